@@ -7,7 +7,20 @@ wraps in-kernel.  N > 1: one process per GPU, weak scaling, global lattice
 256 x 256 x (256 N) cut into z-slabs, deep ghost zones exchanged over RCCL
 (xGMI) on a second stream, overlapped with the interior planes.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size L] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size L] [--strong] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and no more: set-up, clock settle,
+warm-up, the K timed steps, --dump-outputs if asked, one JSON line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the configuration).
+Everything else described below -- the roofline, the check protocols, the CPU
+baselines, the copy-bandwidth probe and the c3_512 / c1_qm1d / frames_256 /
+slab_1gpu / c1_phi4_32 / c5_1024 sub-records -- runs with --full.
+
+--dump-outputs DIR writes the field the timed steps left (this rank's slab, as
+Phi4Lattice.download() returns it) to DIR/phi.npy, float32; above 32 MiB a
+fixed sample of its sites.  The lattice is reset to its seeded start field and
+step counter 0 between the settle phase (whose step count depends on the
+clock) and the warm-up, so the dumped values depend on the arguments alone.
 
 With --gpus N > 1 and no torch.distributed launcher around it, the process
 spawns the N rank processes itself (fresh interpreters, RANK / LOCAL_RANK /
@@ -20,7 +33,7 @@ otherwise time ramping clocks), then W warm-up steps, then EXACTLY K timed steps
 bracketed by barrier + device synchronisation; `value` = all site updates of
 all ranks / max over ranks of that wall time.
 
-Roofline: the dominant kernel is the two-step fused kernel,
+Roofline (--full): the dominant kernel is the two-step fused kernel,
 which moves the field once per two updates and is bound by VALU issue, not
 HBM.  `bound` "valu", `frac` = the launch's VALU-busy SIMD cycles (4 x
 SQ_ACTIVE_INST_VALU from the committed rocprofv3 PMC record of this same
@@ -31,7 +44,7 @@ the same time -- saturates by construction under two-step temporal blocking),
 `frac_hbm_real` (the PMC bytes of a launch over that time) and
 `frac_algorithmic_wall` (8 B per update over the wall time behind `value`).
 
-Also in the line: `multi_rank_check` (stochquant_amd/verify.py: every rank's
+Also in the --full line: `multi_rank_check` (stochquant_amd/verify.py: every rank's
 slab after a fixed check protocol against the golden digests of a single-GPU
 run of the same global lattice -- "pass" / "fail"), and, in the default N = 1
 run, `c3_512`: BASELINE configs[2] (512^3, HBM-resident) measured the same way
@@ -52,6 +65,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0          # MI355X HBM3E spec (MI355X_MICROARCH.md); measured copy peak reported beside it
 BYTES_PER_SITE = 8              # read phi + write phi' (fp32), SURVEY.md §8d
 METRIC = "lattice-site Langevin updates/sec at 256³ fp32; achieved HBM GB/s vs peak"
+INIT_AMP = 0.1                  # phi0 = INIT_AMP * Philox normal (seed 0x5EED)
+DUMP_BYTES = 32 << 20           # --dump-outputs writes at most this much, all ranks together
 
 
 def parse():
@@ -61,6 +76,18 @@ def parse():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--settle-ms", type=float, default=1500.0,
                     help="untimed steps for at least this long before the warm-up (clock settle)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the roofline pass, the multi_rank_check / "
+                         "oracle_check / oracle_check_noise protocols, the copy-bandwidth probe, the CPU baselines "
+                         "and the c3_512 / c1_qm1d / frames_256 / slab_1gpu / c1_phi4_32 / c5_1024 sub-records "
+                         "(each still subject to its own --no-... switch); without it a run sets up, settles, "
+                         "warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the field they left (what Phi4Lattice.download() returns "
+                         "to a caller) as DIR/phi.npy (rank r > 0: DIR/phi_rank<r>.npy), float32; a slab of more "
+                         "than DUMP_BYTES / N bytes as a fixed sample of its sites (seeded by the slab's shape "
+                         "and rank).  The field and step counter are reset to the seeded start before the "
+                         "warm-up, so the same arguments give the same arrays from run to run")
     ap.add_argument("--size", type=int, default=256, help="per-GPU lattice edge (default 256 = config C2)")
     ap.add_argument("--dtau", type=float, default=0.01)
     ap.add_argument("--comm", choices=["auto", "rccl", "p2p", "loopback"], default="auto",
@@ -103,7 +130,11 @@ def parse():
     ap.add_argument("--dry-run", action="store_true",
                     help="set up the ranks and their process group, print each rank's slab and deep-halo "
                          "schedule, touch no GPU (tests the multi-rank launch path on a CPU host)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if not a.full:
+        # a plain run: the headline only, none of the checks, baselines or sub-records
+        a.no_check = a.no_cpu_baseline = a.no_c3 = a.no_c1 = a.no_extra = a.no_c5 = True
+    return a
 
 
 def dry_run(a, world, rank, local, dist):
@@ -362,11 +393,29 @@ def open_with_fallback(make_primary, make_fallback, world, dist):
     return make_fallback(), why
 
 
-def measure(a, lat, world, slab_path, watch=None):
-    """Settle, warm-up, EXACTLY a.steps timed steps (barrier + device sync on both
-    sides, max over ranks), then the roofline pass: the same steps again with one
-    hipEvent pair on the step-kernel stream.  Returns (wall seconds, perf,
-    settle_ms, settle_steps)."""
+def dump_outputs(a, lat, world):
+    """--dump-outputs: this rank's slab as the timed steps left it, float32, to
+    DIR/phi.npy (rank r > 0: DIR/phi_rank<r>.npy).  A slab above this rank's
+    share of DUMP_BYTES is written as a sample: the sites at fixed pseudo-random
+    flat indices (numpy default_rng seeded by the slab's shape and the rank,
+    drawn with replacement), the same in every run and build."""
+    import numpy as np
+    rank = int(os.environ.get("RANK", "0"))
+    f = np.ascontiguousarray(lat.download(), dtype=np.float32)
+    cap = DUMP_BYTES // max(1, world) // f.itemsize
+    if f.size > cap:
+        idx = np.random.default_rng([0x5EED, rank, *f.shape]).integers(0, f.size, cap)
+        f = f.reshape(-1)[idx]
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    np.save(os.path.join(a.dump_outputs, "phi.npy" if rank == 0 else f"phi_rank{rank}.npy"), f)
+
+
+def measure(a, lat, world, slab_path, watch=None, dump=False):
+    """Settle, reset to the seeded start, warm-up, EXACTLY a.steps timed steps
+    (barrier + device sync on both sides, max over ranks); with --dump-outputs
+    (dump) the field they left is written; with --full then the roofline pass:
+    the same steps again with one hipEvent pair on the step-kernel stream.
+    Returns (wall seconds, perf, settle_ms, settle_steps)."""
     import torch
     import torch.distributed as dist
 
@@ -400,6 +449,11 @@ def measure(a, lat, world, slab_path, watch=None):
         if not int(go.item()):
             break
     settle_ms = (time.perf_counter() - t_settle) * 1e3
+    # the settle phase runs as many steps as fit its time: back to the seeded
+    # start field and step counter 0, so that the warm-up and the timed steps
+    # compute the same trajectory in every run with the same arguments
+    lat.init_field(INIT_AMP)
+    lat.step_counter = 0
     phase("warmup")
     lat.step(a.warmup)
     # host bookkeeping while the warm-up steps run, so the device idles only
@@ -417,7 +471,10 @@ def measure(a, lat, world, slab_path, watch=None):
     t = time.perf_counter() - t0
     lat.sync()                 # the library's own join + error check, outside the timed region
     perf = lat.perf()
-    if not a.no_profile_events:
+    if dump:
+        phase("dump_outputs")
+        dump_outputs(a, lat, world)
+    if a.full and not a.no_profile_events:
         phase("roofline_pass")
         # roofline pass: the same K steps again, right behind the wall-timed
         # region (whose launches carry no instrumentation), with ONE hipEvent
@@ -960,18 +1017,20 @@ def run(a, world, rank, watch):
     shape = (L, L, L) if a.strong else (L, L, L * world)
     watch.phase("comm_init", comm=a.comm, shape=list(shape))
     lat, slab_path = make_lattice(a, shape, world, rank, local)
-    lat.init_field(0.1)
-    t, perf, settle_ms, settle_steps = measure(a, lat, world, slab_path, watch)
+    lat.init_field(INIT_AMP)
+    t, perf, settle_ms, settle_steps = measure(a, lat, world, slab_path, watch, dump=a.dump_outputs is not None)
     # sanity: the field stayed finite and bounded (no guard hits)
     m = lat.moments()
     sites_local = lat.nz_local * L * L
     total_updates = float(shape[0] * shape[1] * shape[2]) * a.steps
     value = total_updates / t
     nslabs = a.slabs if (world == 1 and a.comm == "loopback") else 1
-    rl, _, fused = roofline(a, lat, L, world, slab_path, t, perf, nslabs, sites_local)
-    achieved_wall = BYTES_PER_SITE * value / 1e9
-    rl["frac_algorithmic_wall"] = round(achieved_wall / HBM_PEAK_GBPS, 4)
-    rl["achieved_algorithmic_wall_GBps"] = round(achieved_wall, 1)
+    rl = None
+    if a.full:
+        rl, _, fused = roofline(a, lat, L, world, slab_path, t, perf, nslabs, sites_local)
+        achieved_wall = BYTES_PER_SITE * value / 1e9
+        rl["frac_algorithmic_wall"] = round(achieved_wall / HBM_PEAK_GBPS, 4)
+        rl["achieved_algorithmic_wall_GBps"] = round(achieved_wall, 1)
     # self-check (verify.py): the check protocol's slab digests against the
     # golden ones of a single-GPU run of the same global lattice, every rank
     check = "skipped"
@@ -1016,7 +1075,7 @@ def run(a, world, rank, watch):
         try:
             import ctypes
             g = ctypes.c_double()
-            if _lib.load().sq_copy_bandwidth(local, 1 << 30, 20, ctypes.byref(g)) == 0:
+            if a.full and _lib.load().sq_copy_bandwidth(local, 1 << 30, 20, ctypes.byref(g)) == 0:
                 copy = round(g.value, 1)
         except Exception:
             copy = None
@@ -1035,6 +1094,7 @@ def run(a, world, rank, watch):
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
             "settle_ms": round(settle_ms, 1),
             "settle_steps": settle_steps,
             "ms_per_step": t * 1e3 / a.steps,

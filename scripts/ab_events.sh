@@ -7,7 +7,7 @@ mkdir -p $O
 for i in 1 2 3; do
   for mode in ev noev; do
     extra=""; [ $mode = noev ] && extra="--no-profile-events"
-    timeout -k 10 100 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline $extra > $O/${mode}_$i.log 2>&1 || exit 3
+    timeout -k 10 100 python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline $extra > $O/${mode}_$i.log 2>&1 || exit 3
     python3 -c "
 import json
 d=json.loads(open('$O/${mode}_$i.log').read().strip().splitlines()[-1])

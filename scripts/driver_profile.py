@@ -1,7 +1,7 @@
 """Summarise rocprofv3 runs of the DRIVER's bench invocation into the record
 bench.py's roofline reads (profiles/r0N/driver_profile.json: r05, r06).
 
-Inputs (one rocprofv3 run each, all of `python3 bench.py --steps 20 --warmup 5`,
+Inputs (one rocprofv3 run each, all of `python3 bench.py --steps 20 --warmup 5 --full`,
 MI355X_MICROARCH.md §rocprofv3: counters in passes of their own):
   --trace DIR   --kernel-trace --stats  (per-dispatch durations + the stats CSV)
   --fetch DIR   --pmc FETCH_SIZE
@@ -78,7 +78,7 @@ def main():
     ap.add_argument("--fetch", required=True)
     ap.add_argument("--write", required=True)
     ap.add_argument("--sq", required=True)
-    ap.add_argument("--command", default="python3 bench.py --steps 20 --warmup 5")
+    ap.add_argument("--command", default="python3 bench.py --steps 20 --warmup 5 --full")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     groups = fused_groups(a.trace)

@@ -16,8 +16,8 @@ mkdir -p $O
 B="bench.py --steps 400 --warmup 100 --settle-ms 300 --no-cpu-baseline"
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_driver.log 2>&1 || exit 2
-timeout -k 10 200 python bench.py --no-cpu-baseline > $O/bench_2000.log 2>&1 || exit 3
+timeout -k 10 200 python bench.py --steps 20 --warmup 5 --full > $O/bench_driver.log 2>&1 || exit 2
+timeout -k 10 200 python bench.py --full --no-cpu-baseline > $O/bench_2000.log 2>&1 || exit 3
 grep -h '^{' $O/bench_driver.log $O/bench_2000.log | cut -c1-400
 timeout -s KILL 180 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv -- python3 bench.py --steps 2000 --no-cpu-baseline > $O/trace.log 2>&1 || exit 4
 timeout -s KILL 90 rocprofv3 --pmc FETCH_SIZE -d $O/fetch -o run --output-format csv -- python3 $B > $O/fetch.log 2>&1 || exit 5

@@ -9,7 +9,7 @@ a single-GPU run.  `golden_slabs.json` holds those digests, made on one MI355X
 by scripts/make_golden_slabs.py for the bench's weak-scaling lattices
 256 × 256 × 256N and the strong-scaling 1024³, N = 1, 2, 4, 8.
 
-bench.py runs the protocol after its timed region on every rank, gathers the
+bench.py --full runs the protocol after its timed region on every rank, gathers the
 digests and prints "multi_rank_check": "pass" / "fail" (or "no golden").
 """
 import hashlib

@@ -47,6 +47,19 @@ def test_bench_single_rank_under_a_launcher():
     assert d["n_gpus"] == 1 and d["ranks"][0]["plan"] is None
 
 
+def test_only_full_runs_more_than_the_headline(monkeypatch):
+    """Without --full every check, baseline and sub-record is off (and the
+    roofline pass, keyed on `full` itself); with it each keeps its own switch."""
+    import bench
+    extras = ("no_check", "no_cpu_baseline", "no_c3", "no_c1", "no_extra", "no_c5")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 7 and all(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-c3", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and [k for k in extras if getattr(a, k)] == ["no_c3"]
+
+
 def _run_rc(args, env=None, timeout=120):
     e = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "SQ_PHASE_DIR"):
@@ -112,7 +125,7 @@ def test_two_ranks_on_one_gpu_default_transport():
     ranks on GPU 0 with the default transport.  RCCL refuses two ranks on one
     device, so the ranks must agree to fall back to P2P together (bench.py
     open_with_fallback), run, and pass the multi-rank golden-digest check."""
-    d = _run(["--gpus", "2", "--same-device", "--steps", "20", "--warmup", "5", "--no-c3", "--no-c1",
+    d = _run(["--gpus", "2", "--same-device", "--steps", "20", "--warmup", "5", "--full", "--no-c3", "--no-c1",
               "--no-cpu-baseline", "--rank-timeout", "200"], timeout=280)
     assert d["n_gpus"] == 2 and d["value"] and d["value"] > 0
     assert d["multi_rank_check"] == "pass"

@@ -306,9 +306,42 @@ def test_bench_multi_rank_check(gpu, corrupt):
     single-GPU run of the 256 x 256 x 512 lattice: "pass"; with one value of
     rank 1's slab flipped: "fail"."""
     args = ["--gpus", "2", "--comm", "p2p", "--same-device", "--steps", "4", "--warmup", "2",
-            "--settle-ms", "0", "--no-cpu-baseline", "--no-c3"]
+            "--settle-ms", "0", "--full", "--no-cpu-baseline", "--no-c3"]
     if corrupt:
         args += ["--corrupt-rank", "1"]
     d = _bench(args)
     assert d["n_gpus"] == 2 and d["config"]["lattice"] == [256, 256, 512]
     assert d["multi_rank_check"] == ("fail" if corrupt else "pass")
+
+
+@pytest.mark.parametrize("size", [128, 256])
+def test_bench_plain_run_dumps_the_timed_field(gpu, tmp_path, size):
+    """A plain bench.py run (no --full) prints the headline line alone -- no
+    roofline, no check protocol, no sub-record -- and --dump-outputs writes the
+    field its timed steps left: warm-up + steps updates of the seeded start
+    field from step counter 0, whatever the settle phase ran before (it runs at
+    least one batch of 50 steps).  128^3 is written whole, 256^3 (64 MiB) as
+    the fixed sample of bench.DUMP_BYTES; bitwise against the same steps
+    through the library in this process."""
+    import bench
+    steps, warmup = 5, 3
+    d = _bench(["--gpus", "1", "--size", str(size), "--steps", str(steps), "--warmup", str(warmup),
+                "--settle-ms", "0", "--dump-outputs", str(tmp_path)])
+    assert d["metric"] == bench.METRIC and d["unit"] == "site-updates/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "fp32" and d["steps"] == steps and d["settle_steps"] >= 50
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(size ** 3 / (d["ms_per_step"] * 1e-3))
+    assert d["full"] is False and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["multi_rank_check"] == d["oracle_check"] == d["oracle_check_noise"] == "skipped"
+    assert not {"c3_512", "c1_qm1d", "frames_256", "slab_1gpu", "c1_phi4_32", "c5_1024"} & set(d)
+    got = np.load(tmp_path / "phi.npy")
+    assert got.dtype == np.float32 and got.nbytes <= bench.DUMP_BYTES
+    with _lat((size, size, size), dtau=0.01, m2=1.0, lam=1.0, seed=0x5EED, device=0) as L:
+        L.init_field(bench.INIT_AMP)
+        L.step(warmup + steps)
+        ref = L.download()
+    if size == 128:
+        assert got.shape == ref.shape
+    else:
+        idx = np.random.default_rng([0x5EED, 0, *ref.shape]).integers(0, ref.size, bench.DUMP_BYTES // 4)
+        ref = ref.reshape(-1)[idx]
+    assert np.array_equal(got, ref)
