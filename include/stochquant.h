@@ -305,6 +305,42 @@ int sq_phi4_block_stamps(sq_ctx *ctx, unsigned long long *out, int cap, int *nbl
  * at under the chip's power management (bench.py clock_MHz_measured). */
 int sq_phi4_block_clocks(sq_ctx *ctx, unsigned long long *out, int cap, int *nblocks);
 
+/* QM1D replica ensemble: nrep independent chains (SQ_ORDER_JACOBI, Philox
+ * noise, fp64) with the same N, Δt, potID, C, loops and adapt_dtau, advanced
+ * together, one frame per launch, one work-group per replica.  Replica r
+ * behaves exactly -- bit for bit in f, x, xx0, omega, runs, lrgEl, lrgVl, the
+ * tick, every frame's verdict and Δτ after every frame -- as a QM1D context
+ * created with seed = seeds[r] (seeds == NULL: p->seed + r) and given the same
+ * uploads and the same sequence of frame calls: an unstable frame keeps f, x,
+ * xx0, omega and runs but still advances the tick by loops and keeps the new
+ * lrgEl / lrgVl, and the Δτ controller acts per replica.  Adoption and the
+ * controller run on the device, so sq_ens_run_frames issues nframes launches
+ * and reads the verdicts back once.  2 <= N <= 4096, potID 0 or 3.  Not
+ * covered: SQ_ORDER_SERIAL, chains above 4096 sites, and tauhost.o, whose
+ * command line and stdout stay single-chain.
+ * Ranges [first, first + count) outside [0, nrep) give SQ_E_ARG.  Arrays hold
+ * count rows of N doubles (state) or count entries (scalars); in sq_ens_upload
+ * x, xx0, omega and runs may be NULL (zeros), in the getters any pointer may.
+ * stable: nframes * nrep verdicts, frame-major (nullable).  sq_ens_correlator:
+ * per site i < n <= N the mean over the replicas of xx0[i] - x[i] x[mid] and
+ * (err nullable) its standard error sqrt(sum (c_r - mean)^2 / (R (R - 1))), 0
+ * for one replica; sums in double in replica order.  sq_ens_perf: steps = the
+ * steps the replicas executed, site_updates = steps x N, kernel_launches. */
+typedef struct sq_ens sq_ens;
+int sq_ens_create(const sq_params *p, int nrep, const unsigned long long *seeds, sq_ens **out);
+int sq_ens_destroy(sq_ens *e);
+int sq_ens_upload(sq_ens *e, int first, int count, const double *f, const double *x, const double *xx0,
+                  const double *omega, const long *runs);
+int sq_ens_download(sq_ens *e, int first, int count, double *f, double *x, double *xx0, double *omega, long *runs);
+int sq_ens_get_scan(sq_ens *e, int first, int count, int *lrgEl, double *lrgVl, unsigned long long *tick);
+int sq_ens_set_scan(sq_ens *e, int first, int count, const int *lrgEl, const double *lrgVl,
+                    const unsigned long long *tick);
+int sq_ens_get_dtau(sq_ens *e, int first, int count, double *dtau);
+int sq_ens_set_dtau(sq_ens *e, int first, int count, const double *dtau);
+int sq_ens_run_frames(sq_ens *e, int nframes, int *stable);
+int sq_ens_correlator(sq_ens *e, double *mean, double *err, int n);
+int sq_ens_perf(sq_ens *e, sq_perf_t *out);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

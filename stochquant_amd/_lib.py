@@ -86,6 +86,8 @@ _P = ctypes.c_void_p
 _D = ctypes.POINTER(ctypes.c_double)
 _F = ctypes.POINTER(ctypes.c_float)
 _I = ctypes.POINTER(ctypes.c_int)
+_L = ctypes.POINTER(ctypes.c_long)
+_UL = ctypes.POINTER(ctypes.c_ulonglong)
 
 # name -> (restype, argtypes); every symbol here is declared in include/stochquant.h
 SIGNATURES = {
@@ -159,6 +161,17 @@ SIGNATURES = {
     "sq_copy_bandwidth": (ctypes.c_int, [ctypes.c_int, ctypes.c_size_t, ctypes.c_int, _D]),
     "sq_selftest_libm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _F, _F, ctypes.c_longlong]),
     "sq_selftest_bm_tables": (ctypes.c_int, [ctypes.c_int, _F]),
+    "sq_ens_create": (ctypes.c_int, [ctypes.POINTER(SqParams), ctypes.c_int, _UL, ctypes.POINTER(_P)]),
+    "sq_ens_destroy": (ctypes.c_int, [_P]),
+    "sq_ens_upload": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D, _D, _D, _L]),
+    "sq_ens_download": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D, _D, _D, _L]),
+    "sq_ens_get_scan": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I, _D, _UL]),
+    "sq_ens_set_scan": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I, _D, _UL]),
+    "sq_ens_get_dtau": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_ens_set_dtau": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_ens_run_frames": (ctypes.c_int, [_P, ctypes.c_int, _I]),
+    "sq_ens_correlator": (ctypes.c_int, [_P, _D, _D, ctypes.c_int]),
+    "sq_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),
 }
 
 _lib = None

@@ -6,6 +6,7 @@ same contract (`run_tauhost`, `parse_frame_line`) plus thin numpy wrappers of
 the C ABI for the two models:
 
 * `Qm1dChain`  -- tau_kernel.cl time_dev + the tauhost.c frame loop (fp64)
+* `Qm1dEnsemble` -- R such chains per launch, one work-group per replica
 * `Phi4Lattice` -- the 3-D fp32 north-star extension (slab / multi-GPU)
 
 Everything computes on the MI355X through libstochquant.so; nothing here has a
@@ -195,6 +196,143 @@ class Qm1dChain(_Ctx):
         out = np.empty(self.N)
         _lib.call("sq_correlator", self._h, _dptr(out), self.N)
         return out
+
+
+class Qm1dEnsemble:
+    """`replicas` independent Qm1dChain-equivalent chains (Jacobi order, Philox
+    noise) advanced together, one frame per launch, one work-group per replica
+    (sq_ens_*).  Replica r behaves bit for bit as a `Qm1dChain` with
+    seed = seeds[r] (default seed + r) given the same uploads and frame calls;
+    the Δτ controller acts per replica.  2 <= N <= 4096, potID 0 or 3."""
+
+    def __init__(self, N, deltat, deltatau, replicas, seeds=None, pot=3, C=1.0, loops=1000, seed=0x5EED,
+                 adapt_dtau=True, device=0):
+        p = _lib.default_params()
+        p.model = SQ_MODEL_QM1D
+        p.dims[0] = int(N)
+        p.deltat = float(deltat)
+        p.deltatau = float(deltatau)
+        p.pot = int(pot)
+        p.C = float(C)
+        p.loops = int(loops)
+        p.seed = int(seed)
+        p.device = int(device)
+        p.adapt_dtau = 1 if adapt_dtau else 0
+        self._h = ctypes.c_void_p()
+        sp = None
+        if seeds is not None:
+            s = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if s.shape != (int(replicas),):
+                raise ValueError("seeds must have one entry per replica")
+            sp = s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))
+        _lib.call("sq_ens_create", ctypes.byref(p), int(replicas), sp, ctypes.byref(self._h))
+        self.params = p
+        self.N = int(N)
+        self.R = int(replicas)
+
+    def close(self):
+        if self._h:
+            _lib.call("sq_ens_destroy", self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _rows(self, a, k, name):
+        """(N,) -> k equal rows; (k, N) as given."""
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape == (self.N,):
+            a = np.broadcast_to(a, (k, self.N))
+        if a.shape != (k, self.N):
+            raise ValueError(f"{name} must have shape (N,) or ({k}, N)")
+        return np.ascontiguousarray(a)
+
+    def upload(self, f, x=None, xx0=None, omega=0.0, runs=0, first=0):
+        """State of replicas first .. first + k: arrays of shape (N,) go to every
+        replica (k = all of them from `first`), arrays of shape (k, N) to k
+        replicas; omega and runs are scalars or have k entries."""
+        k = None
+        for a in (f, x, xx0):
+            if a is not None and np.ndim(a) == 2:
+                k = np.shape(a)[0]
+        if k is None:
+            k = self.R - int(first)
+        f = self._rows(f, k, "f")
+        x = None if x is None else self._rows(x, k, "x")
+        xx0 = None if xx0 is None else self._rows(xx0, k, "xx0")
+        om = np.ascontiguousarray(np.broadcast_to(np.asarray(omega, dtype=np.float64), (k,)))
+        rn = np.ascontiguousarray(np.broadcast_to(np.asarray(runs, dtype=np.int64), (k,)).astype(ctypes.c_long))
+        _lib.call("sq_ens_upload", self._h, int(first), int(k), _dptr(f), None if x is None else _dptr(x),
+                  None if xx0 is None else _dptr(xx0), _dptr(om), rn.ctypes.data_as(ctypes.POINTER(ctypes.c_long)))
+
+    def download(self, first=0, count=None):
+        k = self.R - int(first) if count is None else int(count)
+        f, x, xx0 = (np.empty((max(k, 0), self.N)) for _ in range(3))
+        om = np.empty(max(k, 0))
+        runs = np.empty(max(k, 0), dtype=ctypes.c_long)
+        _lib.call("sq_ens_download", self._h, int(first), k, _dptr(f), _dptr(x), _dptr(xx0), _dptr(om),
+                  runs.ctypes.data_as(ctypes.POINTER(ctypes.c_long)))
+        return {"f": f, "x": x, "xx0": xx0, "omega": om, "runs": runs.astype(np.int64)}
+
+    def run_frames(self, n):
+        """n frames of every replica back to back (n launches, one read-back);
+        returns the (n, R) bool matrix of verdicts."""
+        st = np.zeros((max(int(n), 0), self.R), dtype=np.int32)
+        _lib.call("sq_ens_run_frames", self._h, int(n), st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return st == 1
+
+    def run_frame(self):
+        """One frame of every replica; returns the (R,) bool array of verdicts."""
+        return self.run_frames(1)[0]
+
+    @property
+    def dtau(self):
+        d = np.empty(self.R)
+        _lib.call("sq_ens_get_dtau", self._h, 0, self.R, _dptr(d))
+        return d
+
+    @dtau.setter
+    def dtau(self, v):
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (self.R,)))
+        _lib.call("sq_ens_set_dtau", self._h, 0, self.R, _dptr(d))
+
+    @property
+    def scan(self):
+        e = np.empty(self.R, dtype=np.int32)
+        v = np.empty(self.R)
+        t = np.empty(self.R, dtype=np.uint64)
+        _lib.call("sq_ens_get_scan", self._h, 0, self.R, e.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(v),
+                  t.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+        return {"lrgEl": e, "lrgVl": v, "tick": t}
+
+    def set_scan(self, lrgEl, lrgVl, tick):
+        """Scalars (every replica) or (R,) arrays."""
+        e = np.ascontiguousarray(np.broadcast_to(np.asarray(lrgEl, dtype=np.int32), (self.R,)))
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(lrgVl, dtype=np.float64), (self.R,)))
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(tick, dtype=np.uint64), (self.R,)))
+        _lib.call("sq_ens_set_scan", self._h, 0, self.R, e.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(v),
+                  t.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+
+    def correlator(self, n=None):
+        """(mean, standard error) over the replicas of xx0 - x * x[mid], per site."""
+        n = self.N if n is None else int(n)
+        mean, err = np.empty(n), np.empty(n)
+        _lib.call("sq_ens_correlator", self._h, _dptr(mean), _dptr(err), n)
+        return mean, err
+
+    def perf(self):
+        p = _lib.SqPerf()
+        _lib.call("sq_ens_perf", self._h, ctypes.byref(p))
+        return {k: getattr(p, k) for k, _ in p._fields_}
 
 
 class Phi4Lattice(_Ctx):
