@@ -30,7 +30,7 @@
 
 float orc_phi4_sigma(float h, double C) { return (float)(sqrt(2.0 * (double)h) * C); }
 /* sigma * sqrt(2 ln 2): the amplitude of the kernels' box_muller_q pairs
- * (sq_api.cpp phi4_base_args, kSqrt2Ln2 = 1.1774100225154747). */
+ * (sq_phi4_steps.cpp phi4_base_args, kSqrt2Ln2 = 1.1774100225154747). */
 float orc_phi4_sigq(float h, double C) { return (float)(sqrt(2.0 * (double)h) * C * 1.1774100225154747); }
 float orc_phi4_lam6(float lam) { return (float)((double)lam / 6.0); }
 

@@ -1,5 +1,5 @@
 // sq_ens.h -- the QM1D replica ensemble (sq_qm1d_ens.hip, the sq_ens_* entry
-// points of sq_api.cpp): R independent chains advanced together, one frame
+// points of sq_ens.cpp): R independent chains advanced together, one frame
 // per launch, one work-group per replica.  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>

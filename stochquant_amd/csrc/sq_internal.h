@@ -1,5 +1,5 @@
 // sq_internal.h -- kernel argument blocks and launchers shared between the
-// kernel translation units and the C-ABI layer (sq_api.cpp).  Not installed.
+// kernel translation units and the C-ABI layer (sq_ctx.h and its sources).  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -702,7 +702,7 @@ __device__ __forceinline__ void frame_fold(const Phi4StepArgs &A, FrameOv &ov) {
             FrameCtl c = *A.fold.cin;
             float T = c.T, V = c.V;
             int fired = -1;
-            for (int j = 0; j < L; ++j) {  // stab_rule (sq_api.cpp)
+            for (int j = 0; j < L; ++j) {  // stab_rule (sq_phi4_frames.cpp)
                 const float M = unord_f32_dev((uint32_t)(sK[j] >> 32)), D = __uint_as_float((uint32_t)sK[j]);
                 const float Aj = __uint_as_float(sAm[j]);
                 const bool f = M > T && D > V;
@@ -1635,7 +1635,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // ------------------------------------------------ device frame control ----
-// After each frame of sq_run_frames (sq_api.cpp phi4_frames_dev), one launch:
+// After each frame of sq_run_frames (sq_phi4_frames.cpp phi4_frames_dev), one launch:
 // the host loop of phi4_frame (record fold, stab_rule, tauhost.c:523-541's Δτ
 // rule) and its rollback, so the next frame is enqueued without a host
 // decision.  Every block folds the frame's records into LDS and takes the
@@ -1653,7 +1653,7 @@ __device__ __forceinline__ float unord_f32_dev(uint32_t o) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
-// The host's frame verdict and Δτ controller (sq_api.cpp phi4_frame + adapt,
+// The host's frame verdict and Δτ controller (sq_phi4_frames.cpp phi4_frame + adapt,
 // tauhost.c:523-529,537-541), operation for operation, on the controller state.
 __device__ __forceinline__ void frame_decide(FrameCtl &c, float T, float V, int fired, int flag) {
     const int st = (flag == 0 && fired < 0) ? 1 : 0;
@@ -1722,7 +1722,7 @@ __global__ __launch_bounds__(256) void phi4_frame_end_kernel(FrameEndArgs E) {
             }
         }
         __syncthreads();
-        if (threadIdx.x == 0 && sFired < 0) {  // stab_rule (sq_api.cpp); every chunk still folds (rec)
+        if (threadIdx.x == 0 && sFired < 0) {  // stab_rule (sq_phi4_frames.cpp); every chunk still folds (rec)
             float T = sT, V = sV;
             for (int j = 0; j < n; ++j) {
                 const bool f = sM[j] > T && sD[j] > V;

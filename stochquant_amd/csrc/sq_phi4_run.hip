@@ -24,7 +24,7 @@
 // bypasses L1.  Every wait is bounded (kRunSpinMax polls); a block that gives
 // up sets bit 2 of *err and stops, and every other block's wait ends at its
 // next poll when it sees *err, so the grid always drains; the host reports the
-// error and the field is then corrupt (sq_api.cpp, gate_check).
+// error and the field is then corrupt (sq_phi4_steps.cpp, gate_check).
 //
 // The site arithmetic is tb_plane's, so a call of n pairs is bit-identical to
 // n phi4_tb2_kernel launches (tests/test_gpu_phi4.py, test_run_kernel_*).

@@ -2,7 +2,7 @@
 // fp64) per launch: one work-group per replica, blockIdx.x = replica, the wave
 // and site tiling of the single-chain register kernel (qm1d_wave_shape,
 // N <= 4096).  Replica r computes, bit for bit, what qm1d_frame_wave and the
-// host bookkeeping of sq_api.cpp (qm1d_frame, adapt) compute for a chain with
+// host bookkeeping of sq_qm1d_host.cpp (qm1d_frame; adapt: sq_phi4_frames.cpp) compute for a chain with
 // that replica's key and state.  What differs from the single-chain path:
 //   * the frame scalars come from the replica's device record (EnsRec), and the
 //     kernel derives h, sigma and sigma_w from the record's Δτ with the host's

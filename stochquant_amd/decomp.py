@@ -1,6 +1,7 @@
 """Slab decomposition of the 3-D lattice along z (the slowest axis).
 
-Mirrors create_phi4() / phi4_block() in csrc/sq_api.cpp: rank r
+Mirrors create_phi4() (csrc/sq_phi4_create.cpp) and phi4_block()
+(csrc/sq_phi4_steps.cpp), DESIGN.md §8: rank r
 of P owns global planes [Lz*r//P, Lz*(r+1)//P) plus a ghost zone of G planes
 on either side (G = steps per halo exchange).  Every G steps one exchange
 sends the G top planes to rank r+1 and the G bottom planes to rank r-1 and

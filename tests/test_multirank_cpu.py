@@ -4,7 +4,7 @@ slab exchange.
 Each rank owns planes [Lz*r/P, Lz*(r+1)/P) plus a ghost zone of G planes on
 either side in two padded ping-pong buffers, exactly as create_phi4 lays them
 out, and executes the product's own schedule (`sq_phi4_block_plan`, the list
-phi4_block in csrc/sq_api.cpp runs on the GPU):
+phi4_block in csrc/sq_phi4_steps.cpp runs on the GPU):
 
 * EXCHANGE: the G top planes to rank r+1, the G bottom planes to rank r-1,
   lower ghosts from r-1, upper ghosts from r+1, in the product's ncclSend /
@@ -43,7 +43,7 @@ def _free_port():
 
 
 def _exchange(bufs, cur, nz, G, world, up, dn):
-    """The product's halo exchange (sq_api.cpp phi4_block, RCCL branch)."""
+    """The product's halo exchange (sq_phi4_steps.cpp phi4_block, RCCL branch)."""
     import torch
     b = bufs[cur]
     top = torch.from_numpy(b[G + nz - G:G + nz].copy())   # my top G planes -> up

@@ -1,4 +1,4 @@
-"""The P2P exchange protocol of round 6 (phi4_block in csrc/sq_api.cpp,
+"""The P2P exchange protocol of round 6 (phi4_block in csrc/sq_phi4_steps.cpp,
 DESIGN.md §8.2), modelled on the CPU and checked under random interleavings.
 
 Each rank's exchange stream B runs, per exchange e = 1, 2, ...:
