@@ -341,6 +341,55 @@ int sq_ens_run_frames(sq_ens *e, int nframes, int *stable);
 int sq_ens_correlator(sq_ens *e, double *mean, double *err, int n);
 int sq_ens_perf(sq_ens *e, sq_perf_t *out);
 
+/* PHI4 lattice ensemble: nrep independent periodic lattices of one shape
+ * (Lx, Ly, Lz) = p->dims, each with its own seed, Δτ, m², λ and C (all start
+ * from p's; sq_phi4_ens_set_params changes them per replica), advanced
+ * together by ONE launch per sq_phi4_ens_step call, one work-group per lattice;
+ * a lattice stays in registers and LDS from the call's first step to its last
+ * and touches device memory only at the call's start and end.  Replica r is
+ * bit for bit the SQ_COMM_NONE PHI4 context with the same shape, parameters,
+ * seed = seeds[r] (seeds == NULL: p->seed + r), step counter and start field
+ * after the same number of sq_step steps, and sq_phi4_ens_init_field gives it
+ * that context's sq_init_field.  Step calls are additive: nsteps in one call
+ * equal any split of them into several calls.
+ * Shapes: Lx in {8, 16, 32, 64}, Ly >= 2, Lz >= 2, Lx Ly Lz <= 32768; comm must
+ * be SQ_COMM_NONE; the parameter bound of a PHI4 context (finite, clamp^2
+ * finite in fp32, dtau * drift(clamp) < 1e30) holds per replica at creation
+ * and in sq_phi4_ens_set_params, which changes nothing when one replica of
+ * its range breaks it.  These are SQ_E_ARG before the device is looked for.
+ * Raw steps only: the frame machinery of sq_run_frame (stability rule,
+ * rollback, Δτ controller) is not part of the ensemble.  Its guard flag per
+ * replica is: 1 when any step since the last clear clamped a site or met a
+ * NaN (max |phi'| before the guard >= clamp).
+ * Ranges [first, first + count) outside [0, nrep) give SQ_E_ARG.  Field rows
+ * hold Lz*Ly*Lx floats, z slowest; in set_params / get_params any array may be
+ * NULL (left alone / not reported).  sq_phi4_ens_step: with every = k > 0 and
+ * series != NULL the kernel records after each k-th step of the call, from
+ * the on-chip field, S1 = sum phi, S2 = sum phi^2, S4 = sum phi^4 and NN = sum
+ * over sites and mu = x, y, z of phi(x) phi(x + mu) (sites converted to
+ * double, products and sums in double): series holds (nsteps / k) * nrep * 4
+ * doubles, measurement-major, read back once at the end of the call.
+ * sq_phi4_ens_moments: out5 = count rows of {S1, S2, S4, NN, max |phi|} of the
+ * current fields.  sq_phi4_ens_flags: the guard flags (flags nullable), then
+ * cleared when clear != 0.  sq_phi4_ens_perf: steps = the steps the replicas
+ * executed, site_updates = steps x sites, kernel_launches. */
+typedef struct sq_phi4_ens sq_phi4_ens;
+int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *seeds, sq_phi4_ens **out);
+int sq_phi4_ens_destroy(sq_phi4_ens *e);
+int sq_phi4_ens_upload(sq_phi4_ens *e, int first, int count, const float *phi);
+int sq_phi4_ens_download(sq_phi4_ens *e, int first, int count, float *phi);
+int sq_phi4_ens_init_field(sq_phi4_ens *e, float amp);
+int sq_phi4_ens_set_params(sq_phi4_ens *e, int first, int count, const double *dtau, const double *m2,
+                           const double *lambda, const double *C);
+int sq_phi4_ens_get_params(sq_phi4_ens *e, int first, int count, double *dtau, double *m2, double *lambda,
+                           double *C);
+int sq_phi4_ens_get_step(sq_phi4_ens *e, int first, int count, unsigned long long *step);
+int sq_phi4_ens_set_step(sq_phi4_ens *e, int first, int count, const unsigned long long *step);
+int sq_phi4_ens_step(sq_phi4_ens *e, int nsteps, int every, double *series);
+int sq_phi4_ens_moments(sq_phi4_ens *e, int first, int count, double *out5);
+int sq_phi4_ens_flags(sq_phi4_ens *e, int first, int count, int *flags, int clear);
+int sq_phi4_ens_perf(sq_phi4_ens *e, sq_perf_t *out);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

@@ -172,6 +172,19 @@ SIGNATURES = {
     "sq_ens_run_frames": (ctypes.c_int, [_P, ctypes.c_int, _I]),
     "sq_ens_correlator": (ctypes.c_int, [_P, _D, _D, ctypes.c_int]),
     "sq_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),
+    "sq_phi4_ens_create": (ctypes.c_int, [ctypes.POINTER(SqParams), ctypes.c_int, _UL, ctypes.POINTER(_P)]),
+    "sq_phi4_ens_destroy": (ctypes.c_int, [_P]),
+    "sq_phi4_ens_upload": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F]),
+    "sq_phi4_ens_download": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F]),
+    "sq_phi4_ens_init_field": (ctypes.c_int, [_P, ctypes.c_float]),
+    "sq_phi4_ens_set_params": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D, _D, _D]),
+    "sq_phi4_ens_get_params": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D, _D, _D]),
+    "sq_phi4_ens_get_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _UL]),
+    "sq_phi4_ens_set_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _UL]),
+    "sq_phi4_ens_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_phi4_ens_moments": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_phi4_ens_flags": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int]),
+    "sq_phi4_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),
 }
 
 _lib = None

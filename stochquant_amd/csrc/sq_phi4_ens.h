@@ -1,0 +1,59 @@
+// sq_phi4_ens.h -- the phi^4 lattice ensemble (sq_phi4_ens.hip, the
+// sq_phi4_ens_* entry points of sq_phi4_ens.cpp): R independent periodic
+// lattices of one shape advanced together, one launch per call, one work-group
+// per lattice, the field on-chip between the call's first and last step.
+// Raw steps only: no frame control (stability rule, rollback, Δτ controller).
+// Not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace sq {
+
+constexpr int kPhi4EnsMaxSites = 32768;  // 128 KiB of fp32: one LDS image of the lattice
+constexpr int kPhi4EnsMaxLanes = 1024;
+constexpr int kPhi4EnsLdsBytes = 160 * 1024;
+// LDS behind the image(s): per wave 4 doubles (the sums) and one float (max |phi|), for 16 waves
+constexpr int kPhi4EnsScratchBytes = 16 * 4 * 8 + 16 * 4;
+
+// One replica's step coefficients, derived from its Δτ, m², λ, C as
+// phi4_base_args derives a context's (sq_phi4_steps.cpp), its Philox key and
+// its step counter at the time the records were last written; the kernels
+// only read them.
+struct Phi4EnsRec {
+    float h, m2, lam6, sig, sigq;
+    uint32_t k0, k1;
+    uint32_t pad;
+    unsigned long long step;
+};
+
+struct Phi4EnsArgs {
+    float *field;            // [R][Lz][Ly][Lx], replica r at offset r * sites
+    const Phi4EnsRec *rec;   // [R]
+    int *flags;              // [R] guard flags: set to 1, never cleared, by the step kernel
+    double *series;          // [nsteps / every][R][4] = S1, S2, S4, NN, device-visible (pinned host memory);
+                             // nullable: no measurements
+    int Lx, Ly, Lz;
+    int nsteps, every;
+    float clampv;
+    unsigned long long adv;  // steps every replica has run since the records were written
+};
+
+// Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
+// quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and
+// whether two LDS images fit (one barrier per step instead of two).
+struct Phi4EnsShape {
+    int K, T;
+    bool two;
+    int lds_bytes;
+};
+Phi4EnsShape phi4_ens_shape(int sites);
+
+// nsteps steps of every replica in one launch (grid = nrep work-groups).
+hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s);
+// out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
+hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
+// phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.
+hipError_t phi4_ens_init_launch(const Phi4EnsArgs &a, int nrep, float amp, hipStream_t s);
+
+}  // namespace sq

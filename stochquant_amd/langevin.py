@@ -8,6 +8,7 @@ the C ABI for the two models:
 * `Qm1dChain`  -- tau_kernel.cl time_dev + the tauhost.c frame loop (fp64)
 * `Qm1dEnsemble` -- R such chains per launch, one work-group per replica
 * `Phi4Lattice` -- the 3-D fp32 north-star extension (slab / multi-GPU)
+* `Phi4Ensemble` -- R small φ⁴ lattices per launch, each on-chip in one work-group
 
 Everything computes on the MI355X through libstochquant.so; nothing here has a
 CPU path.
@@ -509,6 +510,168 @@ class Phi4Lattice(_Ctx):
             raise ValueError(f"every handle blob has {n} bytes")
         buf = (ctypes.c_ubyte * (n * len(blobs))).from_buffer_copy(b"".join(blobs))
         _lib.call("sq_p2p_connect", self._h, buf, len(blobs))
+
+
+class Phi4Ensemble:
+    """`replicas` independent periodic φ⁴ lattices of one shape (Lx, Ly, Lz),
+    each with its own seed, Δτ, m², λ and C, advanced together: one launch per
+    `step` call, one work-group per lattice, the lattice on-chip for every step
+    of the call (sq_phi4_ens_*).  Replica r is bit for bit the `Phi4Lattice`
+    (comm="none") of the same shape, parameters, seed, step counter and start
+    field.  Lx in {8, 16, 32, 64}, Ly, Lz >= 2, at most 32,768 sites.  Raw
+    steps only: no frames (stability rule, rollback, Δτ controller).
+
+    dtau, m2, lam and C are scalars or length-R sequences; seeds defaults to
+    seed + r."""
+
+    def __init__(self, shape, replicas, dtau=0.01, m2=1.0, lam=1.0, C=1.0, seeds=None, seed=0x5EED, clamp=1000.0,
+                 device=0):
+        R = int(replicas)
+        per = [np.asarray(v, dtype=np.float64) for v in (dtau, m2, lam, C)]
+        for v in per:
+            if v.ndim > 1 or (v.ndim == 1 and v.shape != (R,)):
+                raise ValueError("dtau, m2, lam and C are scalars or have one entry per replica")
+        p = _lib.default_params()
+        p.model = SQ_MODEL_PHI4
+        for i in range(3):
+            p.dims[i] = int(shape[i])
+        # the create call checks the parameters it is given: replica 0's, the others' arrive through set_params
+        p.deltatau, p.m2, p.lambda_, p.C = (float(v.reshape(-1)[0]) for v in per)
+        p.seed = int(seed)
+        p.clamp = float(clamp)
+        p.device = int(device)
+        p.comm = SQ_COMM_NONE
+        self._h = ctypes.c_void_p()
+        sp = None
+        if seeds is not None:
+            s = np.ascontiguousarray(seeds, dtype=np.uint64)
+            if s.shape != (R,):
+                raise ValueError("seeds must have one entry per replica")
+            sp = s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong))
+        _lib.call("sq_phi4_ens_create", ctypes.byref(p), R, sp, ctypes.byref(self._h))
+        self.params = p
+        self.shape = tuple(int(s) for s in shape)
+        self.R = R
+        if any(v.ndim == 1 for v in per):
+            try:
+                self.set_params(*per)
+            except Exception:
+                self.close()
+                raise
+
+    def close(self):
+        if self._h:
+            _lib.call("sq_phi4_ens_destroy", self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def lattice_shape(self):
+        return (self.shape[2], self.shape[1], self.shape[0])  # numpy order: z, y, x
+
+    def _count(self, first, count):
+        return self.R - int(first) if count is None else int(count)
+
+    def upload(self, phi, first=0):
+        """Fields of replicas first .. first + k: an array of one lattice's shape
+        (Lz, Ly, Lx) goes to every replica from `first`, (k, Lz, Ly, Lx) to k replicas."""
+        a = np.asarray(phi, dtype=np.float32)
+        ls = self.lattice_shape
+        if a.shape == ls:
+            a = np.broadcast_to(a, (max(self.R - int(first), 0),) + ls)
+        if a.ndim != 4 or a.shape[1:] != ls:
+            raise ValueError(f"fields must have shape {ls} or (k,) + {ls}")
+        a = np.ascontiguousarray(a)
+        _lib.call("sq_phi4_ens_upload", self._h, int(first), a.shape[0], _fptr(a))
+
+    def download(self, first=0, count=None):
+        k = self._count(first, count)
+        a = np.empty((max(k, 0),) + self.lattice_shape, dtype=np.float32)
+        _lib.call("sq_phi4_ens_download", self._h, int(first), k, _fptr(a))
+        return a
+
+    def init_field(self, amp):
+        """Replica r: the `Phi4Lattice.init_field(amp)` of its seed."""
+        _lib.call("sq_phi4_ens_init_field", self._h, float(amp))
+
+    def set_params(self, dtau=None, m2=None, lam=None, C=None, first=0, count=None):
+        """Per-replica parameters of replicas first .. first + count (scalars or
+        `count` entries; None leaves a parameter alone).  Raises, changing
+        nothing, when a replica would break the context's parameter bound."""
+        k = self._count(first, count)
+        arrs = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64),
+                                                                           (max(k, 0),)))
+                for v in (dtau, m2, lam, C)]
+        _lib.call("sq_phi4_ens_set_params", self._h, int(first), k, *[None if a is None else _dptr(a) for a in arrs])
+
+    def get_params(self, first=0, count=None):
+        k = self._count(first, count)
+        out = {n: np.empty(max(k, 0)) for n in ("dtau", "m2", "lam", "C")}
+        _lib.call("sq_phi4_ens_get_params", self._h, int(first), k, *[_dptr(out[n]) for n in ("dtau", "m2", "lam", "C")])
+        return out
+
+    @property
+    def dtau(self):
+        return self.get_params()["dtau"]
+
+    @dtau.setter
+    def dtau(self, v):
+        self.set_params(dtau=v)
+
+    @property
+    def step_counter(self):
+        s = np.empty(self.R, dtype=np.uint64)
+        _lib.call("sq_phi4_ens_get_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+        return s
+
+    @step_counter.setter
+    def step_counter(self, v):
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64), (self.R,)))
+        _lib.call("sq_phi4_ens_set_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+
+    def step(self, n=1, every=0):
+        """n steps of every replica in one launch.  every = k > 0: returns the
+        (n // k, R, 4) array of S1 = Σφ, S2 = Σφ², S4 = Σφ⁴ and NN = Σ over
+        sites and the three forward links of φ(x) φ(x + μ), recorded after each
+        k-th step from the on-chip field; otherwise None."""
+        n, every = int(n), int(every)
+        if every <= 0:
+            _lib.call("sq_phi4_ens_step", self._h, n, 0, None)
+            return None
+        ser = np.zeros((max(n, 0) // every, self.R, 4))
+        _lib.call("sq_phi4_ens_step", self._h, n, every, _dptr(ser) if ser.size else None)
+        return ser
+
+    def moments(self, first=0, count=None):
+        """{"S1", "S2", "S4", "NN", "maxabs"}: (count,) arrays of the current fields' sums."""
+        k = self._count(first, count)
+        out = np.empty((max(k, 0), 5))
+        _lib.call("sq_phi4_ens_moments", self._h, int(first), k, _dptr(out))
+        return {n: out[:, i].copy() for i, n in enumerate(("S1", "S2", "S4", "NN", "maxabs"))}
+
+    def flags(self, clear=False, first=0, count=None):
+        """(count,) bool array: a step since the last clear clamped a site or met a NaN."""
+        k = self._count(first, count)
+        f = np.zeros(max(k, 0), dtype=np.int32)
+        _lib.call("sq_phi4_ens_flags", self._h, int(first), k, f.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                  1 if clear else 0)
+        return f != 0
+
+    def perf(self):
+        p = _lib.SqPerf()
+        _lib.call("sq_phi4_ens_perf", self._h, ctypes.byref(p))
+        return {k: getattr(p, k) for k, _ in p._fields_}
 
 
 def connect_p2p(lat, group=None):
