@@ -357,10 +357,34 @@ int sq_ens_perf(sq_ens *e, sq_perf_t *out);
  * finite in fp32, dtau * drift(clamp) < 1e30) holds per replica at creation
  * and in sq_phi4_ens_set_params, which changes nothing when one replica of
  * its range breaks it.  These are SQ_E_ARG before the device is looked for.
- * Raw steps only: the frame machinery of sq_run_frame (stability rule,
- * rollback, Δτ controller) is not part of the ensemble.  Its guard flag per
- * replica is: 1 when any step since the last clear clamped a site or met a
- * NaN (max |phi'| before the guard >= clamp).
+ * The guard flag per replica is: 1 when any executed step since the last
+ * clear, raw or in a frame, clamped a site or met a NaN (max |phi'| before the
+ * guard >= clamp).
+ * Frames: sq_phi4_ens_run_frames runs nframes frames of every replica in ONE
+ * launch, each replica decided by its own work-group as sq_run_frames decides
+ * a context: a frame is p->loops steps (p->loops < 1: SQ_E_ARG here, not at
+ * creation), the stability rule on the replica's carried T and V, the
+ * rollback to the frame's start on failure, and with p->adapt_dtau the Δτ
+ * controller (x 0.95 on failure, / 0.95 after 11 stable frames).  Replica r
+ * equals that context frame for frame in verdicts, Δτ, field, T, V and
+ * records.  A frame whose rule has fired skips its remaining steps (the
+ * verdict is settled); the step counter advances by p->loops per frame either
+ * way, and a retried frame draws fresh noise.  stable and dtau hold nframes *
+ * nrep entries, frame-major (dtau: Δτ after the frame); series is nullable and
+ * holds nframes * nrep * 4 doubles, S1, S2, S4, NN of the field after each
+ * frame's verdict (the adopted field, or the frame's start again after a
+ * rollback).  nframes == 0 is a no-op.  Afterwards get_params reports the
+ * adapted Δτ and sq_phi4_ens_step runs at it; a Δτ set between calls holds
+ * from the next frame on and keeps the count of stable frames, as sq_set_dtau.
+ * sq_phi4_ens_stability: per replica of the range TV = {T, V}, the firing step
+ * of its last frame (-1: none) and the first n <= p->loops per-step records
+ * M, D, A of that frame (count rows of n; valid through the firing step, or
+ * all p->loops when the rule did not fire; n > 0 before the first frames call
+ * is SQ_E_ARG); every output is nullable.  The records are a device buffer of
+ * nrep * p->loops * 3 floats from the first frames call on (12 MB at nrep =
+ * 1024, loops = 1000).  sq_phi4_ens_set_stability sets T and V and marks the
+ * replicas initialised, as sq_phi4_set_stability; otherwise a replica's first
+ * frame takes them from its start field, and an upload does not reset them.
  * Ranges [first, first + count) outside [0, nrep) give SQ_E_ARG.  Field rows
  * hold Lz*Ly*Lx floats, z slowest; in set_params / get_params any array may be
  * NULL (left alone / not reported).  sq_phi4_ens_step: with every = k > 0 and
@@ -372,7 +396,8 @@ int sq_ens_perf(sq_ens *e, sq_perf_t *out);
  * sq_phi4_ens_moments: out5 = count rows of {S1, S2, S4, NN, max |phi|} of the
  * current fields.  sq_phi4_ens_flags: the guard flags (flags nullable), then
  * cleared when clear != 0.  sq_phi4_ens_perf: steps = the steps the replicas
- * executed, site_updates = steps x sites, kernel_launches. */
+ * executed (a frame that exited early counts the steps it ran, not
+ * p->loops), site_updates = steps x sites, kernel_launches. */
 typedef struct sq_phi4_ens sq_phi4_ens;
 int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *seeds, sq_phi4_ens **out);
 int sq_phi4_ens_destroy(sq_phi4_ens *e);
@@ -386,6 +411,10 @@ int sq_phi4_ens_get_params(sq_phi4_ens *e, int first, int count, double *dtau, d
 int sq_phi4_ens_get_step(sq_phi4_ens *e, int first, int count, unsigned long long *step);
 int sq_phi4_ens_set_step(sq_phi4_ens *e, int first, int count, const unsigned long long *step);
 int sq_phi4_ens_step(sq_phi4_ens *e, int nsteps, int every, double *series);
+int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series);
+int sq_phi4_ens_stability(sq_phi4_ens *e, int first, int count, double *TV /*[count][2]*/, int *fired, float *M,
+                          float *D, float *A, int n);
+int sq_phi4_ens_set_stability(sq_phi4_ens *e, int first, int count, const double *T, const double *V);
 int sq_phi4_ens_moments(sq_phi4_ens *e, int first, int count, double *out5);
 int sq_phi4_ens_flags(sq_phi4_ens *e, int first, int count, int *flags, int clear);
 int sq_phi4_ens_perf(sq_phi4_ens *e, sq_perf_t *out);

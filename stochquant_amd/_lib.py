@@ -182,6 +182,9 @@ SIGNATURES = {
     "sq_phi4_ens_get_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _UL]),
     "sq_phi4_ens_set_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _UL]),
     "sq_phi4_ens_step": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_phi4_ens_run_frames": (ctypes.c_int, [_P, ctypes.c_int, _I, _D, _D]),
+    "sq_phi4_ens_stability": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _I, _F, _F, _F, ctypes.c_int]),
+    "sq_phi4_ens_set_stability": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D]),
     "sq_phi4_ens_moments": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
     "sq_phi4_ens_flags": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int]),
     "sq_phi4_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),

@@ -2,7 +2,9 @@
 // points of the C ABI: R lattices per launch (sq_phi4_ens.hip).  The host
 // keeps every replica's parameters and step counter; the device records hold
 // the coefficients derived from them and are rewritten before the next launch
-// whenever a setter changed something.
+// whenever a setter changed something.  Frames (sq_phi4_ens_run_frames) are
+// decided in the kernel; the host mirrors every replica's frame state between
+// calls and uploads it before each one.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -28,6 +30,12 @@ struct sq_phi4_ens {
     size_t series_cap = 0;               // ... in doubles
     double *mom = nullptr;               // [R][5]
     bool rec_dirty = true;               // the device records are behind rep[]
+    std::vector<sq::Phi4EnsFrameState> fst;  // [R] frame state, current between calls
+    sq::Phi4EnsFrameState *fst_dev = nullptr;
+    float *frecs = nullptr;              // [R][3][loops] the last frame's records (first frames call on)
+    int *fr_stable = nullptr;            // [fr_cap][R] a frames call's verdicts ...
+    double *fr_dtau = nullptr;           // ... and Δτ
+    size_t fr_cap = 0;                   // ... in frames
     unsigned long long adv = 0;          // steps run since the records were written
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
@@ -102,6 +110,15 @@ void release_phi4_ens(sq_phi4_ens *e) {
     (void)hipFree(e->flags);
     (void)hipHostFree(e->series);
     (void)hipFree(e->mom);
+    (void)hipFree(e->fst_dev);
+    (void)hipFree(e->frecs);
+    (void)hipFree(e->fr_stable);
+    (void)hipFree(e->fr_dtau);
+    e->fst_dev = nullptr;
+    e->frecs = nullptr;
+    e->fr_stable = nullptr;
+    e->fr_dtau = nullptr;
+    e->fr_cap = 0;
     e->field = nullptr;
     e->rec = nullptr;
     e->flags = nullptr;
@@ -141,6 +158,8 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
     e->R = nrep;
     e->sites = (size_t)(Lx * Ly * Lz);
     e->rep.resize((size_t)nrep);
+    e->fst.assign((size_t)nrep, sq::Phi4EnsFrameState{});
+    for (auto &f : e->fst) f.fired = -1;
     for (int r = 0; r < nrep; ++r)
         e->rep[r] = sq_phi4_ens::Rep{p->deltatau, p->m2, p->lambda, p->C,
                                      seeds ? seeds[r] : p->seed + (unsigned long long)r, 0ull};
@@ -150,6 +169,7 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         SQ_HIP(hipMalloc(&e->rec, sizeof(sq::Phi4EnsRec) * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->flags, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->mom, sizeof(double) * 5 * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->fst_dev, sizeof(sq::Phi4EnsFrameState) * (size_t)nrep));
         SQ_HIP(hipMemset(e->field, 0, bytes));
         SQ_HIP(hipMemset(e->flags, 0, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -288,6 +308,112 @@ int sq_phi4_ens_step(sq_phi4_ens *e, int nsteps, int every, double *series) {
     e->adv += (unsigned long long)nsteps;
     for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
     e->steps_total += (long long)nsteps * e->R;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
+    if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
+    if (nframes == 0) return SQ_OK;
+    if (!stable || !dtau) return fail(SQ_E_ARG, "null argument");
+    DeviceGuard g(e->dev);
+    const int L = e->p.loops;
+    const size_t R = (size_t)e->R, n = (size_t)nframes;
+    int rc = ens_sync_recs(e);
+    if (rc) return rc;
+    if (!e->frecs) {
+        SQ_HIP(hipMalloc(&e->frecs, sizeof(float) * 3 * (size_t)L * R));
+        SQ_HIP(hipMemset(e->frecs, 0, sizeof(float) * 3 * (size_t)L * R));
+        SQ_HIP(hipDeviceSynchronize());  // the memset ran on the null stream
+    }
+    if (n > e->fr_cap) {
+        (void)hipFree(e->fr_stable);
+        (void)hipFree(e->fr_dtau);
+        e->fr_stable = nullptr;
+        e->fr_dtau = nullptr;
+        e->fr_cap = 0;
+        SQ_HIP(hipMalloc(&e->fr_stable, sizeof(int) * n * R));
+        SQ_HIP(hipMalloc(&e->fr_dtau, sizeof(double) * n * R));
+        e->fr_cap = n;
+    }
+    const size_t nd = series ? n * R * 4 : 0;
+    if (nd > e->series_cap) {  // pinned, written by the kernel (sq_phi4_ens_step)
+        (void)hipHostFree(e->series);
+        e->series = nullptr;
+        e->series_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
+        e->series_cap = nd;
+    }
+    for (size_t r = 0; r < R; ++r) {  // a setter may have changed them since the last call
+        e->fst[r].dtau = e->rep[r].dtau;
+        e->fst[r].C = e->rep[r].C;
+    }
+    SQ_HIP(hipMemcpyAsync(e->fst_dev, e->fst.data(), sizeof(sq::Phi4EnsFrameState) * R, hipMemcpyHostToDevice,
+                          e->stream));
+    sq::Phi4EnsArgs a = ens_args(e);
+    a.series = nd ? e->series : nullptr;
+    sq::Phi4EnsFrameArgs f{};
+    f.st = e->fst_dev;
+    f.stable = e->fr_stable;
+    f.dtau = e->fr_dtau;
+    f.recs = e->frecs;
+    f.nframes = nframes;
+    f.loops = L;
+    f.adapt = e->p.adapt_dtau ? 1 : 0;
+    SQ_HIP(sq::phi4_ens_frames_launch(a, f, e->R, e->stream));
+    e->launches++;
+    SQ_HIP(hipMemcpyAsync(e->fst.data(), e->fst_dev, sizeof(sq::Phi4EnsFrameState) * R, hipMemcpyDeviceToHost,
+                          e->stream));
+    SQ_HIP(hipMemcpyAsync(stable, e->fr_stable, sizeof(int) * n * R, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipMemcpyAsync(dtau, e->fr_dtau, sizeof(double) * n * R, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    for (size_t r = 0; r < R; ++r) {
+        e->rep[r].dtau = e->fst[r].dtau;
+        e->rep[r].step += (unsigned long long)nframes * (unsigned long long)L;  // rolled-back frames too
+        e->steps_total += e->fst[r].exec;
+    }
+    e->rec_dirty = true;  // Δτ and the counters moved
+    return SQ_OK;
+}
+
+int sq_phi4_ens_stability(sq_phi4_ens *e, int first, int count, double *TV, int *fired, float *M, float *D, float *A,
+                          int n) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && (!M || !D || !A))) return fail(SQ_E_ARG, "bad record arguments");
+    if (n > (e->frecs ? e->p.loops : 0)) return fail(SQ_E_ARG, "n exceeds the last frame's steps");
+    for (int r = 0; r < count; ++r) {
+        const sq::Phi4EnsFrameState &f = e->fst[(size_t)(first + r)];
+        if (TV) {
+            TV[2 * r] = f.T;
+            TV[2 * r + 1] = f.V;
+        }
+        if (fired) fired[r] = f.fired;
+    }
+    if (n == 0 || count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t L = (size_t)e->p.loops;
+    std::vector<float> h((size_t)count * 3 * L);
+    SQ_HIP(hipMemcpy(h.data(), e->frecs + (size_t)first * 3 * L, sizeof(float) * h.size(), hipMemcpyDeviceToHost));
+    float *rows[3] = {M, D, A};
+    for (int r = 0; r < count; ++r)
+        for (int k = 0; k < 3; ++k)
+            memcpy(rows[k] + (size_t)r * (size_t)n, h.data() + ((size_t)r * 3 + (size_t)k) * L, sizeof(float) * (size_t)n);
+    return SQ_OK;
+}
+
+int sq_phi4_ens_set_stability(sq_phi4_ens *e, int first, int count, const double *T, const double *V) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!T || !V) return fail(SQ_E_ARG, "null argument");
+    for (int r = 0; r < count; ++r) {
+        sq::Phi4EnsFrameState &f = e->fst[(size_t)(first + r)];
+        f.T = (float)T[r];
+        f.V = (float)V[r];
+        f.init = 1;
+    }
     return SQ_OK;
 }
 

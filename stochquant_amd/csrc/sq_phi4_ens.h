@@ -2,8 +2,9 @@
 // sq_phi4_ens_* entry points of sq_phi4_ens.cpp): R independent periodic
 // lattices of one shape advanced together, one launch per call, one work-group
 // per lattice, the field on-chip between the call's first and last step.
-// Raw steps only: no frame control (stability rule, rollback, Δτ controller).
-// Not installed.
+// Raw steps (phi4_ens_step_launch) or whole frames decided in the kernel
+// (phi4_ens_frames_launch: per replica the stability rule, the rollback and
+// the Δτ controller of DESIGN.md §7).  Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +16,9 @@ constexpr int kPhi4EnsMaxLanes = 1024;
 constexpr int kPhi4EnsLdsBytes = 160 * 1024;
 // LDS behind the image(s): per wave 4 doubles (the sums) and one float (max |phi|), for 16 waves
 constexpr int kPhi4EnsScratchBytes = 16 * 4 * 8 + 16 * 4;
+// the frames kernel's words behind that: three rotating step records (u64 key, u32 max |phi'|) and the two
+// maxima of the first frame's start field
+constexpr int kPhi4EnsFrameScratchBytes = kPhi4EnsScratchBytes + 3 * 8 + 3 * 4 + 2 * 4 + 4;
 
 // One replica's step coefficients, derived from its Δτ, m², λ, C as
 // phi4_base_args derives a context's (sq_phi4_steps.cpp), its Philox key and
@@ -30,13 +34,34 @@ struct Phi4EnsRec {
 struct Phi4EnsArgs {
     float *field;            // [R][Lz][Ly][Lx], replica r at offset r * sites
     const Phi4EnsRec *rec;   // [R]
-    int *flags;              // [R] guard flags: set to 1, never cleared, by the step kernel
+    int *flags;              // [R] guard flags: set to 1, never cleared, by the step and frames kernels
     double *series;          // [nsteps / every][R][4] = S1, S2, S4, NN, device-visible (pinned host memory);
                              // nullable: no measurements
     int Lx, Ly, Lz;
     int nsteps, every;
     float clampv;
     unsigned long long adv;  // steps every replica has run since the records were written
+};
+
+// One replica's frame state, read at the start of a frames launch and written
+// back at its end (the host keeps a mirror and uploads it before every launch).
+struct Phi4EnsFrameState {
+    double dtau, C;  // Δτ of the next frame (the controller's double), noise amplitude
+    float T, V;      // stability rule: last step's max phi', running max |phi'| (never rolled back)
+    int init;        // T, V are set (else the first frame takes them from its start field)
+    int cnt;         // stable frames since the last Δτ change by the controller
+    int fired;       // the last frame's firing step, -1 none
+    int flag;        // its guard flag
+    int exec;        // steps the last launch executed (early exits run fewer than nframes * loops)
+    int pad;
+};
+
+struct Phi4EnsFrameArgs {
+    Phi4EnsFrameState *st;  // [R]
+    int *stable;            // [nframes][R] verdicts
+    double *dtau;           // [nframes][R] Δτ after the frame
+    float *recs;            // [R][3][loops]: M | D | A of the replica's last frame, through its firing step
+    int nframes, loops, adapt;
 };
 
 // Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
@@ -51,6 +76,9 @@ Phi4EnsShape phi4_ens_shape(int sites);
 
 // nsteps steps of every replica in one launch (grid = nrep work-groups).
 hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s);
+// nframes frames of every replica in one launch (grid = nrep work-groups); a.series nullable:
+// [nframes][R][4] sums of the field after each frame's verdict.  a.nsteps / a.every are not used.
+hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, int nrep, hipStream_t s);
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

@@ -27,6 +27,11 @@
 // step_lo, step_hi} through tb_noise, keyed by the replica's seed.  A replica
 // whose sig is 0 takes the noise-off instance of the update, as a context with
 // C = 0 does.  No work-group ever waits for another one.
+//
+// phi4_ens_frames_kernel runs whole frames the same way: per
+// step the block's stability record behind the step's own barrier, the rule,
+// an early exit once it has fired; per frame the verdict, the Δτ controller
+// and the store to / reload from the replica's HBM field, its snapshot.
 #define SQ_PHI4_KERNELS_ONLY
 #include "sq_phi4.hip"
 #include "sq_phi4_ens.h"
@@ -263,6 +268,252 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const P
     if (am >= E.clampv) E.flags[r] = 1;
 }
 
+// frame_sites (sq_phi4.hip) for a lane that may own no quad here: the step's
+// stability record of the lane's float4 o into f.  am takes
+// every site (mp: site_update4's max |phi'| after the guard); the per-site
+// (m, d) update runs only in waves where some float4 reaches the wave's
+// running maximum mw, which keeps the wave's maximum key exact.  The inputs of
+// o are read back from the image, which holds them until the step's store:
+// the lane keeps no second copy of its quad.  Every lane of the wave calls it
+// (the wave scan needs them all); a lane without a quad comes with o = -inf
+// and mp = 0, below every site, and is tested for only on the per-site path
+// (fl made opaque there: no exec mask per quad kept across the step).
+template <bool NZ>
+__device__ __forceinline__ void ens_frame_sites(const Phi4StepArgs &A, FrameAcc &f, uint32_t fl, const float4 &o,
+                                                const float4 *old, const f32x4n &xi, float mp) {
+    f.am = vmax(f.am, mp);
+    if (__ballot(mp >= f.mw) == 0ull) return;  // max |o| >= max o
+    const float o4 = vmax(vmax3(o.x, o.y, o.z), o.w);  // the guard's output: never NaN
+    if (__ballot(o4 >= f.mw) == 0ull) return;
+    asm volatile("" : "+v"(fl));
+    if (fl & kEnsValid) {
+        const float4 c = *old;
+        const float s = NZ ? A.sigq : 0.f;
+        stab_site(f, o.x, c.x, xi.a, s);
+        stab_site(f, o.y, c.y, xi.b, s);
+        stab_site(f, o.z, c.z, xi.c, s);
+        stab_site(f, o.w, c.w, xi.d, s);
+    }
+    f.mw = dpp_all_max_f(f.m);
+}
+
+// ens_step for a frame: the same update, and the step's record in fa.  The
+// quads of lanes without one hold -inf (phi4_ens_frames_kernel sets them).
+template <int K, bool NZ>
+__device__ __forceinline__ void ens_step_fr(const Phi4StepArgs &A, const EnsGeo &g, float4 (&c)[K],
+                                            const uint32_t (&fl)[K], const float *img, uint32_t slo, uint32_t shi,
+                                            FrameAcc &fa) {
+    const float4 *img4 = reinterpret_cast<const float4 *>(img);
+    const int T = blockDim.x;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        uint32_t f = fl[j];
+        int q = (int)threadIdx.x + j * T;
+        asm volatile("" : "+v"(f), "+v"(q));  // as ens_step
+        f32x4n xi{};
+        float mp = 0.f;
+        if (f & kEnsValid) {
+            const EnsNbr n = ens_nbr(g, q, f);
+            const float4 up = img4[n.up], dn = img4[n.dn], zm = img4[n.zm], zp = img4[n.zp];
+            const float lft = img[n.lf], rgt = img[n.rg];
+            xi = tb_noise<NZ>(A, 0u, (uint32_t)q, slo, shi);
+            c[j] = site_update4<NZ>(c[j], lft, rgt, up, dn, zm, zp, xi, A, false, f32x2{A.m2, A.m2}, &mp);
+        }
+        ens_frame_sites<NZ>(A, fa, f, c[j], img4 + q, xi, mp);
+    }
+}
+
+// n frames of replica blockIdx.x, all decided here: per step the block's
+// record (M, D, A) through LDS atomic maxima behind the step's own barrier,
+// the stability rule on the carried T and V, an early exit once it has fired;
+// per frame the verdict, the Δτ controller and the new coefficients
+// (frame_decide / phi4_base_args, operation for operation), then the store
+// of the adopted field to HBM -- the next frame's snapshot -- or the reload
+// of registers and image from it.  The noise counter advances by loops per
+// frame either way.
+//
+// The step records rotate through three LDS slots: step s posts to slot s % 3
+// before its barrier, every lane reads it after, and lane 0 then clears slot
+// (s + 2) % 3 -- last read before this barrier, next posted after the next one.
+template <int K>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const Phi4EnsArgs E,
+                                                                            const Phi4EnsFrameArgs F, const int two) {
+    const int r = blockIdx.x;
+    const EnsGeo g = ens_geo(E);
+    const Phi4EnsRec rc = E.rec[r];
+    const Phi4EnsFrameState st = F.st[r];
+    Phi4StepArgs A{};
+    A.h = rc.h;
+    A.m2 = rc.m2;
+    A.lam6 = rc.lam6;
+    A.sig = rc.sig;
+    A.sigq = rc.sigq;
+    A.clampv = E.clampv;
+    A.k0 = rc.k0;
+    A.k1 = rc.k1;
+    const bool nz = rc.sig != 0.0f;
+    float *img0 = reinterpret_cast<float *>(ens_smem);
+    float *img1 = two ? img0 + 4 * g.Q : img0;
+    char *sb = ens_smem + (size_t)(two ? 2 : 1) * 16 * (size_t)g.Q;
+    double *scr = reinterpret_cast<double *>(sb);
+    unsigned long long *fk = reinterpret_cast<unsigned long long *>(sb + kPhi4EnsScratchBytes);  // [3]
+    uint32_t *fw = reinterpret_cast<uint32_t *>(fk + 3);  // [0..2] max |phi'| of a step, [3], [4] the start field's
+    if (threadIdx.x < 3) fk[threadIdx.x] = 0ull;
+    if (threadIdx.x < 5) fw[threadIdx.x] = 0u;
+    float4 c[K];
+    uint32_t fl[K];
+    ens_load<K>(E, g, r, c, fl, img0);  // ends in a barrier
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (!(fl[j] & kEnsValid)) c[j].x = c[j].y = c[j].z = c[j].w = -__builtin_inff();  // ens_step_fr
+    const int T = blockDim.x;
+    const bool lane0 = (threadIdx.x & 63) == 0;
+    float sT = st.T, sV = st.V;
+    if (!st.init) {  // the replica's first frame ever: max phi and max |phi| of its start field
+        float mp = -__builtin_inff(), ma = 0.f;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (fl[j] & kEnsValid) {
+                mp = fmaxf(mp, fmaxf(fmaxf(c[j].x, c[j].y), fmaxf(c[j].z, c[j].w)));
+                ma = fmaxf(ma, fmaxf(fmaxf(fabsf(c[j].x), fabsf(c[j].y)), fmaxf(fabsf(c[j].z), fabsf(c[j].w))));
+            }
+        mp = dpp_all_max_f(mp);
+        ma = dpp_all_max_f(ma);
+        if (lane0) {
+            atomicMax(&fw[3], ord_f32(mp));
+            atomicMax(&fw[4], __float_as_uint(ma));
+        }
+        __syncthreads();
+        sT = unord_f32_dev(fw[3]);
+        sV = __uint_as_float(fw[4]);
+    }
+    sT = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sT)));
+    sV = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sV)));
+    double dtau = st.dtau;
+    int cnt = st.cnt, fired = -1, gflag = 0, exec = 0, sticky = 0;
+    int slot = 0;
+    const int L = F.loops;
+    const unsigned long long s0 = rc.step + E.adv;
+    float *cur = img0, *oth = img1;
+    float4 *gf = reinterpret_cast<float4 *>(E.field + (size_t)r * (size_t)(4 * g.Q));
+    float *recM = F.recs + (size_t)r * 3 * (size_t)L, *recD = recM + L, *recA = recD + L;
+    for (int f = 0; f < F.nframes; ++f) {
+        fired = -1;
+        gflag = 0;
+        const unsigned long long sf = s0 + (unsigned long long)f * (unsigned long long)L;
+        for (int t = 0; t < L; ++t) {
+            const unsigned long long s = sf + (unsigned long long)t;
+            const uint32_t slo = (uint32_t)s, shi = (uint32_t)(s >> 32);
+            FrameAcc fa = frame_acc();
+            if (nz) ens_step_fr<K, true>(A, g, c, fl, cur, slo, shi, fa);
+            else ens_step_fr<K, false>(A, g, c, fl, cur, slo, shi, fa);
+            // the wave's key from the lanes that hold its maximum (frame_flush2), its max |phi'| by a scan
+            if (fa.m >= fa.mw && fa.mw > -__builtin_inff())
+                atomicMax(&fk[slot], ((unsigned long long)ord_f32(fa.m) << 32) | __float_as_uint(fa.d));
+            const uint32_t wa = (uint32_t)dpp_all_max_i((int)__float_as_uint(fminf(fa.am, A.clampv)));
+            if (lane0) atomicMax(&fw[slot], wa);
+            if (!two) __syncthreads();  // one image: every wave has read it
+            {
+                float *x = cur;
+                cur = oth;
+                oth = x;
+            }
+            float4 *cur4 = reinterpret_cast<float4 *>(cur);
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (fl[j] & kEnsValid) cur4[(int)threadIdx.x + j * T] = c[j];
+            __syncthreads();
+            const unsigned long long key = fk[slot];
+            const uint32_t kM = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+            const float M = unord_f32_dev(kM);
+            const float D = __uint_as_float(__builtin_amdgcn_readfirstlane((uint32_t)key));
+            const float Am = __uint_as_float(__builtin_amdgcn_readfirstlane(fw[slot]));
+            const int clr = slot == 0 ? 2 : slot - 1;
+            slot = slot == 2 ? 0 : slot + 1;
+            if (threadIdx.x == 0) {
+                fk[clr] = 0ull;
+                fw[clr] = 0u;
+                recM[t] = M;
+                recD[t] = D;
+                recA[t] = Am;
+            }
+            ++exec;
+            if (Am >= E.clampv) gflag = 1;  // some site was clamped (NaN -> +clamp)
+            const bool fire = M > sT && D > sV;  // stab_rule (sq_phi4_frames.cpp)
+            sT = M;
+            sV = sV < Am ? Am : sV;
+            if (fire) {
+                fired = t;
+                break;  // the verdict is settled, T and V frozen: the rest of the frame is skipped
+            }
+        }
+        sticky |= gflag;
+        const int stable = (gflag == 0 && fired < 0) ? 1 : 0;
+        if (F.adapt) {  // frame_decide
+            if (stable) {
+                if (cnt > 10) {
+                    cnt = 0;
+                    dtau /= 0.950;
+                }
+                cnt += 1;
+            } else {
+                dtau *= 0.950;
+                cnt = 0;
+            }
+        }
+        const float hf = (float)dtau;  // phi4_base_args
+        A.h = hf;
+        A.sig = (float)(__builtin_sqrt(2.0 * (double)hf) * st.C);
+        A.sigq = (float)(__builtin_sqrt(2.0 * (double)hf) * st.C * kSqrt2Ln2);
+        // q opaque per frame: hoisted out of the frame loop, the K 64-bit addresses of the lane's quads
+        // take 2 K registers for the whole call
+        if (stable) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                int q = (int)threadIdx.x + j * T;
+                asm volatile("" : "+v"(q));
+                if (fl[j] & kEnsValid) gf[q] = c[j];
+            }
+        } else {
+            // every wave is past the last step's barrier and reads no image before the next one
+            float4 *cur4 = reinterpret_cast<float4 *>(cur);
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                int q = (int)threadIdx.x + j * T;
+                asm volatile("" : "+v"(q));
+                if (fl[j] & kEnsValid) {
+                    c[j] = gf[q];
+                    cur4[q] = c[j];
+                }
+            }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            F.stable[(size_t)f * gridDim.x + (size_t)r] = stable;
+            F.dtau[(size_t)f * gridDim.x + (size_t)r] = dtau;
+        }
+        if (E.series != nullptr) {
+            double sm[4];
+            float mx;
+            ens_sums<K>(g, c, fl, cur, sm, mx);
+            ens_fold(sm, mx, scr, E.series + 4 * ((size_t)f * gridDim.x + (size_t)r), false);
+        }
+    }
+    if (threadIdx.x == 0) {
+        Phi4EnsFrameState o = st;
+        o.dtau = dtau;
+        o.T = sT;
+        o.V = sV;
+        o.init = 1;
+        o.cnt = cnt;
+        o.fired = fired;
+        o.flag = gflag;
+        o.exec = exec;
+        F.st[r] = o;
+        if (sticky) E.flags[r] = 1;
+    }
+}
+
 template <int K>
 __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_moments_kernel(const Phi4EnsArgs E, const int first,
                                                                              double *out) {
@@ -331,6 +582,27 @@ hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s) {
     hipError_t e = ens_lds_attr(fn, sh.lds_bytes);
     if (e != hipSuccess) return e;
     return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.lds_bytes, s);
+}
+
+hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
+        f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr)
+        return hipErrorInvalidValue;
+    const int sites = a.Lx * a.Ly * a.Lz;
+    const Phi4EnsShape sh = phi4_ens_shape(sites);
+    // the images as phi4_ens_shape lays them out, with the frame records' words behind the scratch
+    int two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes <= kPhi4EnsLdsBytes ? 1 : 0;
+    const int bytes = (two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsFrameArgs fq = f;
+    void *args[] = {&q, &fq, &two};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_frames_kernel<1>
+                     : sh.K == 2 ? (const void *)&phi4_ens_frames_kernel<2>
+                     : sh.K == 4 ? (const void *)&phi4_ens_frames_kernel<4>
+                                 : (const void *)&phi4_ens_frames_kernel<8>;
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
 }
 
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s) {

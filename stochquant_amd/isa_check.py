@@ -78,17 +78,30 @@ def store_data_hazards(text, wait_states=2):
     return found
 
 
+def _bundles(fat):
+    """The offload bundles of a .hip_fatbin section: a library linked from several
+    device sources holds one per source, back to back (each padded to a page)."""
+    data = open(fat, "rb").read()
+    starts = sorted(m.start() for m in re.finditer(rb"__CLANG_OFFLOAD_BUNDLE__|CCOB", data))
+    return [data[a:b] for a, b in zip(starts, starts[1:] + [len(data)])] or [data]
+
+
 def kernel_metadata(lib):
     """{kernel name: {"private": private_segment_fixed_size, "vgpr": vgpr_count,
-    "vgpr_spill": vgpr_spill_count}} from the code object's AMDGPU metadata."""
+    "vgpr_spill": vgpr_spill_count}} from the AMDGPU metadata of every code
+    object in the library (one per device source)."""
+    text = ""
     with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, "fat.bin"), os.path.join(d, "k.co")
+        fat, one, co = os.path.join(d, "fat.bin"), os.path.join(d, "one.bin"), os.path.join(d, "k.co")
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", lib,
                         os.path.join(d, "x.o")], check=True, capture_output=True)
-        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
-                        f"--targets={TARGET}", f"--output={co}"], check=True, capture_output=True)
-        text = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                              text=True).stdout
+        for blob in _bundles(fat):
+            with open(one, "wb") as fh:
+                fh.write(blob)
+            subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={one}",
+                            f"--targets={TARGET}", f"--output={co}"], check=True, capture_output=True)
+            text += subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True,
+                                   capture_output=True, text=True).stdout
     out = {}
     for block in text.split("    .name:")[1:]:
         name = block.split()[0]

@@ -519,13 +519,16 @@ class Phi4Ensemble:
     of the call (sq_phi4_ens_*).  Replica r is bit for bit the `Phi4Lattice`
     (comm="none") of the same shape, parameters, seed, step counter and start
     field.  Lx in {8, 16, 32, 64}, Ly, Lz >= 2, at most 32,768 sites.  Raw
-    steps only: no frames (stability rule, rollback, Δτ controller).
+    steps (`step`) or whole frames (`run_frames`): `loops` steps, the stability
+    rule, the rollback and, with `adapt_dtau`, the Δτ controller, decided per
+    replica inside the kernel, one launch per call, as `Phi4Lattice.run_frames`
+    decides them for one lattice.
 
     dtau, m2, lam and C are scalars or length-R sequences; seeds defaults to
     seed + r."""
 
     def __init__(self, shape, replicas, dtau=0.01, m2=1.0, lam=1.0, C=1.0, seeds=None, seed=0x5EED, clamp=1000.0,
-                 device=0):
+                 device=0, loops=100, adapt_dtau=True):
         R = int(replicas)
         per = [np.asarray(v, dtype=np.float64) for v in (dtau, m2, lam, C)]
         for v in per:
@@ -541,6 +544,9 @@ class Phi4Ensemble:
         p.clamp = float(clamp)
         p.device = int(device)
         p.comm = SQ_COMM_NONE
+        p.loops = int(loops)
+        p.adapt_dtau = 1 if adapt_dtau else 0
+        self._frames_run = False
         self._h = ctypes.c_void_p()
         sp = None
         if seeds is not None:
@@ -652,6 +658,45 @@ class Phi4Ensemble:
         ser = np.zeros((max(n, 0) // every, self.R, 4))
         _lib.call("sq_phi4_ens_step", self._h, n, every, _dptr(ser) if ser.size else None)
         return ser
+
+    def run_frames(self, n, measure=False):
+        """n frames of every replica in one launch: (stable (n, R) bool, dtau
+        (n, R) after each frame), and with `measure` the (n, R, 4) sums S1, S2,
+        S4, NN of each replica's field after the frame's verdict (the frame's
+        start field again after a rollback)."""
+        n = int(n)
+        st = np.zeros((max(n, 0), self.R), dtype=np.int32)
+        dt = np.zeros((max(n, 0), self.R))
+        ser = np.zeros((max(n, 0), self.R, 4)) if measure else None
+        _lib.call("sq_phi4_ens_run_frames", self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
+                  None if ser is None else _dptr(ser))
+        if n > 0:
+            self._frames_run = True
+        return (st != 0, dt) if ser is None else (st != 0, dt, ser)
+
+    def run_frame(self):
+        """One frame of every replica; (R,) bool: stable."""
+        return self.run_frames(1)[0][0]
+
+    def stability(self, first=0, count=None, n=None):
+        """The stability rule's state per replica: {"T", "V", "fired" (step of the
+        last frame it fired at, -1 none): (count,) arrays; "M", "D", "A": (count,
+        n) per-step records of the last frame, valid through the firing step}.
+        n defaults to `loops` once a frame has run."""
+        k = self._count(first, count)
+        n = (self.params.loops if self._frames_run else 0) if n is None else int(n)
+        tv = np.zeros((max(k, 0), 2))
+        fired = np.zeros(max(k, 0), dtype=np.int32)
+        M, D, A = (np.zeros((max(k, 0), max(n, 0)), dtype=np.float32) for _ in range(3))
+        _lib.call("sq_phi4_ens_stability", self._h, int(first), k, _dptr(tv),
+                  fired.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _fptr(M), _fptr(D), _fptr(A), n)
+        return {"T": tv[:, 0].copy(), "V": tv[:, 1].copy(), "fired": fired, "M": M, "D": D, "A": A}
+
+    def set_stability(self, T, V, first=0, count=None):
+        """Set the carried T and V (scalars or `count` entries) and mark the replicas initialised."""
+        k = self._count(first, count)
+        t, v = (np.ascontiguousarray(np.broadcast_to(np.asarray(x, dtype=np.float64), (max(k, 0),))) for x in (T, V))
+        _lib.call("sq_phi4_ens_set_stability", self._h, int(first), k, _dptr(t), _dptr(v))
 
     def moments(self, first=0, count=None):
         """{"S1", "S2", "S4", "NN", "maxabs"}: (count,) arrays of the current fields' sums."""
