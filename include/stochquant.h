@@ -397,8 +397,16 @@ int sq_ens_perf(sq_ens *e, sq_perf_t *out);
  * current fields.  sq_phi4_ens_flags: the guard flags (flags nullable), then
  * cleared when clear != 0.  sq_phi4_ens_perf: steps = the steps the replicas
  * executed (a frame that exited early counts the steps it ran, not
- * p->loops), site_updates = steps x sites, kernel_launches. */
+ * p->loops), site_updates = steps x sites, kernel_launches.
+ *
+ * sq_phi4_ens_shape_info needs no device and no handle: for dims = {Lx, Ly,
+ * Lz} it reports the work-group shape the launchers give such a lattice, from
+ * the function they call themselves: out = {K float4 quads per lane, T lanes,
+ * LDS images and dynamic LDS bytes of the step launch, the same two of the
+ * frames launch, LDS bytes of the moments launch, the LDS limit in bytes}.
+ * SQ_E_ARG for exactly the shapes sq_phi4_ens_create refuses. */
 typedef struct sq_phi4_ens sq_phi4_ens;
+int sq_phi4_ens_shape_info(const int dims[3], int out[8]);
 int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *seeds, sq_phi4_ens **out);
 int sq_phi4_ens_destroy(sq_phi4_ens *e);
 int sq_phi4_ens_upload(sq_phi4_ens *e, int first, int count, const float *phi);

@@ -173,6 +173,7 @@ SIGNATURES = {
     "sq_ens_correlator": (ctypes.c_int, [_P, _D, _D, ctypes.c_int]),
     "sq_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),
     "sq_phi4_ens_create": (ctypes.c_int, [ctypes.POINTER(SqParams), ctypes.c_int, _UL, ctypes.POINTER(_P)]),
+    "sq_phi4_ens_shape_info": (ctypes.c_int, [_I, _I]),
     "sq_phi4_ens_destroy": (ctypes.c_int, [_P]),
     "sq_phi4_ens_upload": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F]),
     "sq_phi4_ens_download": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _F]),

@@ -50,6 +50,15 @@ int ens_range(const sq_phi4_ens *e, int first, int count) {
     return SQ_OK;
 }
 
+// What is wrong with a lattice shape, nullptr for a legal one (sq_phi4_ens_create, sq_phi4_ens_shape_info).
+const char *ens_dims_error(long long Lx, long long Ly, long long Lz) {
+    if (Lx != 8 && Lx != 16 && Lx != 32 && Lx != 64) return "a phi^4 ensemble needs Lx in {8, 16, 32, 64}";
+    if (Ly < 2 || Lz < 2) return "a phi^4 ensemble needs Ly >= 2 and Lz >= 2";
+    if (Ly > sq::kPhi4EnsMaxSites || Lz > sq::kPhi4EnsMaxSites || Lx * Ly * Lz > sq::kPhi4EnsMaxSites)
+        return "a phi^4 ensemble needs Lx Ly Lz <= 32768 sites (one LDS image per lattice)";
+    return nullptr;
+}
+
 // create_phi4's parameter bound, per replica (the guard needs every update of a
 // field inside [-clamp, clamp] to be finite or an infinity, never NaN)
 bool ens_params_ok(double cl, double h, double m2, double lambda, double C) {
@@ -137,10 +146,7 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
     if (p->model != SQ_MODEL_PHI4) return fail(SQ_E_ARG, "a phi^4 ensemble needs SQ_MODEL_PHI4");
     if (p->comm != SQ_COMM_NONE) return fail(SQ_E_ARG, "a phi^4 ensemble needs SQ_COMM_NONE");
     const long long Lx = p->dims[0], Ly = p->dims[1], Lz = p->dims[2];
-    if (Lx != 8 && Lx != 16 && Lx != 32 && Lx != 64) return fail(SQ_E_ARG, "a phi^4 ensemble needs Lx in {8, 16, 32, 64}");
-    if (Ly < 2 || Lz < 2) return fail(SQ_E_ARG, "a phi^4 ensemble needs Ly >= 2 and Lz >= 2");
-    if (Ly > sq::kPhi4EnsMaxSites || Lz > sq::kPhi4EnsMaxSites || Lx * Ly * Lz > sq::kPhi4EnsMaxSites)
-        return fail(SQ_E_ARG, "a phi^4 ensemble needs Lx Ly Lz <= 32768 sites (one LDS image per lattice)");
+    if (const char *why = ens_dims_error(Lx, Ly, Lz)) return fail(SQ_E_ARG, why);
     if (nrep < 1) return fail(SQ_E_ARG, "nrep must be >= 1");
     if (!ens_params_ok(p->clamp, p->deltatau, p->m2, p->lambda, p->C))
         return fail(SQ_E_ARG, "PHI4 parameters must be finite with dtau > 0, clamp^2 finite in fp32 and "
@@ -182,6 +188,21 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         return fail(rc, msg);
     }
     *out = e;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_shape_info(const int dims[3], int out[8]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
+    out[0] = s.K;
+    out[1] = s.T;
+    out[2] = s.two ? 2 : 1;
+    out[3] = s.lds_bytes;
+    out[4] = s.fr_two ? 2 : 1;
+    out[5] = s.fr_lds_bytes;
+    out[6] = s.mom_lds_bytes;
+    out[7] = sq::kPhi4EnsLdsBytes;
     return SQ_OK;
 }
 

@@ -65,12 +65,17 @@ struct Phi4EnsFrameArgs {
 };
 
 // Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
-// quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and
-// whether two LDS images fit (one barrier per step instead of two).
+// quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and per
+// launch whether two LDS images fit (one barrier per step instead of two) and
+// the dynamic LDS it asks for: the image(s), then the launch's scratch.  The
+// three launchers and sq_phi4_ens_shape_info take every number from here.
 struct Phi4EnsShape {
     int K, T;
-    bool two;
+    bool two;           // the step launch
     int lds_bytes;
+    bool fr_two;        // the frames launch (kPhi4EnsFrameScratchBytes behind the images)
+    int fr_lds_bytes;
+    int mom_lds_bytes;  // the moments launch: always one image
 };
 Phi4EnsShape phi4_ens_shape(int sites);
 

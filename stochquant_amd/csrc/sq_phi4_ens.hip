@@ -564,6 +564,10 @@ Phi4EnsShape phi4_ens_shape(int sites) {
     s.T = (((Q + s.K - 1) / s.K) + 63) / 64 * 64;
     s.two = 2 * 4 * sites + kPhi4EnsScratchBytes <= kPhi4EnsLdsBytes;
     s.lds_bytes = (s.two ? 2 : 1) * 4 * sites + kPhi4EnsScratchBytes;
+    // the frames launch: the same layout, with the frame records' words behind the scratch
+    s.fr_two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes <= kPhi4EnsLdsBytes;
+    s.fr_lds_bytes = (s.fr_two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes;
+    s.mom_lds_bytes = 4 * sites + kPhi4EnsScratchBytes;
     return s;
 }
 
@@ -588,11 +592,9 @@ hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &
     if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
         f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr)
         return hipErrorInvalidValue;
-    const int sites = a.Lx * a.Ly * a.Lz;
-    const Phi4EnsShape sh = phi4_ens_shape(sites);
-    // the images as phi4_ens_shape lays them out, with the frame records' words behind the scratch
-    int two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes <= kPhi4EnsLdsBytes ? 1 : 0;
-    const int bytes = (two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz);
+    int two = sh.fr_two ? 1 : 0;
+    const int bytes = sh.fr_lds_bytes;
     Phi4EnsArgs q = a;
     Phi4EnsFrameArgs fq = f;
     void *args[] = {&q, &fq, &two};
@@ -607,9 +609,8 @@ hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &
 
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s) {
     if (!ens_shape_ok(a) || first < 0 || count < 1 || out == nullptr) return hipErrorInvalidValue;
-    const int sites = a.Lx * a.Ly * a.Lz;
-    const Phi4EnsShape sh = phi4_ens_shape(sites);
-    const int bytes = 4 * sites + kPhi4EnsScratchBytes;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz);
+    const int bytes = sh.mom_lds_bytes;
     Phi4EnsArgs q = a;
     void *args[] = {&q, &first, &out};
     const void *fn = sh.K == 1   ? (const void *)&phi4_ens_moments_kernel<1>

@@ -565,6 +565,20 @@ class Phi4Ensemble:
                 self.close()
                 raise
 
+    @staticmethod
+    def shape_info(shape):
+        """The work-group shape the launchers give a lattice of `shape`
+        (sq_phi4_ens_shape_info; no device needed): {"K": float4 quads per lane,
+        "T": lanes, "images" / "lds_bytes": LDS images and dynamic LDS bytes of
+        the step launch, "frames_images" / "frames_lds_bytes": of the frames
+        launch, "moments_lds_bytes", "lds_limit"}.  Raises StochQuantError
+        (SQ_E_ARG) for a shape the constructor refuses."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 8)()
+        _lib.call("sq_phi4_ens_shape_info", dims, out)
+        return dict(zip(("K", "T", "images", "lds_bytes", "frames_images", "frames_lds_bytes", "moments_lds_bytes",
+                         "lds_limit"), (int(v) for v in out)))
+
     def close(self):
         if self._h:
             _lib.call("sq_phi4_ens_destroy", self._h)

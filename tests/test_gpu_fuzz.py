@@ -5,6 +5,10 @@
     multi-segment waves), Ly including partial wave tiles, Lz from 1 (the
     periodic self-neighbour case) upward; C = 0 bit-identical, C = 1 within the
     per-step bound of test_gpu_phi4.py.
+  * phi^4 ensemble: legal shapes spread over the four K classes of its
+    work-group, two replicas with different parameters; C = 0 and C = 1 (with
+    the device's Box-Muller factors) bit-identical, series rows within the
+    fsum bound.
   * QM1D serial order: random N, loops, Δτ and potID 0 frames with injected
     reference noise, bit-identical frame by frame.
 """
@@ -45,6 +49,57 @@ def test_phi4_random_shapes(gpu, oracle_mod, Lx, Ly, Lz, steps, C, seed, dtau):
         err = np.abs(got.astype(np.float64) - ref)
         tol_report(f"fuzz{shape},dtau={dtau}", err, steps, ref, STEP_RTOL)
         assert np.all(err <= steps * (STEP_ATOL + STEP_RTOL * np.abs(ref)))
+
+
+# phi^4 ensemble: site counts of the four K classes (K = 1: <= 4,096 sites, 2: <= 8,192, 4: <= 16,384, 8: <= 32,768)
+_ENS_BANDS = [(256, 4096), (4097, 8192), (8193, 16384), (16385, 32768)]
+
+
+@st.composite
+def _ens_shapes(draw):
+    """Lx, then the target site count of a drawn K class, then a factorisation
+    Ly Lz of target // Lx (Lz rounds down: the site count may fall short of
+    the target by less than a plane)."""
+    Lx = draw(st.sampled_from([8, 16, 32, 64]))
+    lo, hi = _ENS_BANDS[draw(st.integers(0, 3))]
+    planes = draw(st.integers(lo, hi)) // Lx              # >= 4
+    Ly = draw(st.integers(2, planes // 2))
+    return (Lx, Ly, planes // Ly)
+
+
+@settings(max_examples=30, deadline=None, derandomize=True,
+          suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
+@given(shape=_ens_shapes(), steps=st.integers(1, 3), every=st.integers(0, 2), C=st.sampled_from([0.0, 1.0]),
+       seed=st.integers(0, 2 ** 40), dtau=st.sampled_from([(0.005, 0.02), (0.02, 0.05), (0.05, 0.005)]),
+       m2=st.sampled_from([(0.5, -0.5), (1.0, 0.25)]), lam=st.sampled_from([(1.0, 2.0), (4.0, 0.5)]))
+def test_phi4_ens_random_shapes(gpu, oracle_mod, bm_tables, shape, steps, every, C, seed, dtau, m2, lam):
+    """The ensemble at random legal shapes over all four K, two replicas with
+    different Δτ, m², λ and seeds: C = 0 bit for bit the oracle, C = 1 bit for
+    bit the oracle with the device's Box-Muller factors; the series rows within
+    2 n u Σ|t| of the exactly rounded sums (test_gpu_phi4_ens.py) of the
+    oracle's field at that step."""
+    import contextlib
+    from stochquant_amd import Phi4Ensemble
+    from test_gpu_phi4_ens import _exact_sums
+    info = Phi4Ensemble.shape_info(shape)                  # raises if the strategy left the legal shapes
+    seeds = [seed, seed + 12345]
+    ps = [oracle_mod.phi4_params(shape, dtau[r], m2[r], lam[r], seeds[r], C=C) for r in range(2)]
+    mode = oracle_mod.device_transcendentals(bm_tables) if C else contextlib.nullcontext()
+    with mode:
+        ref = [oracle_mod.phi4_init(ps[r], 0.8) for r in range(2)]
+        with Phi4Ensemble(shape, 2, dtau=dtau, m2=m2, lam=lam, C=C, seeds=seeds) as E:
+            E.upload(np.stack(ref))
+            ser = E.step(steps, every=every)
+            got = E.download()
+        assert (ser is None) if every == 0 else (ser.shape == (steps // every, 2, 4))
+        for r in range(2):
+            for s in range(steps):
+                ref[r] = oracle_mod.phi4_step(ps[r], ref[r], s)
+                if every and (s + 1) % every == 0:
+                    exact, bound, _ = _exact_sums(ref[r])
+                    err = np.abs(ser[(s + 1) // every - 1, r] - exact)
+                    assert np.all(err <= bound), (shape, info, r, s, err, bound)
+            assert np.array_equal(got[r], ref[r]), (shape, info, r, C, np.max(np.abs(got[r] - ref[r])))
 
 
 def _exact(res):

@@ -3,11 +3,10 @@ lattices per launch, each on-chip in one work-group.
 
 Replica r must be bit for bit the single context (Phi4Lattice, comm="none") of
 the same shape, parameters, seed, step counter and start field, hence also the
-oracle's.  The shapes cover every work-group shape of the kernel: one wave
-(8 x 2 x 2, where both y- and both z-neighbours are the same site), K = 1 with
-a partial last wave (16 x 4 x 31, odd Lz), 13 waves (32 x 8 x 13), K = 2
-(64 x 16 x 8, a row wider than a wave's 16-lane DPP row), and the two lattices
-at the LDS limit, K = 8 with one LDS image (32^3 and 64 x 16 x 32).
+oracle's.  The shapes are test_phi4_ens_shapes.GPU_SHAPES; that file's CPU
+test asserts that they hold a lattice of every work-group shape the launchers
+can pick (K, LDS images, owned quads that do not exist), and every test here
+first asserts that its shape still gets the work-group shape listed there.
 
 Tolerances: bitwise everywhere except (a) the mathematical oracle, whose bound
 is the suite's per-step fp32 bound (conftest.PHI4_STEP_ATOL / RTOL), and (b)
@@ -22,10 +21,16 @@ import numpy as np
 import pytest
 
 from conftest import PHI4_STEP_ATOL, PHI4_STEP_RTOL, tol_report
+from test_phi4_ens_shapes import GPU_SHAPES, assert_shape
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(8, 2, 2), (8, 8, 8), (16, 4, 31), (32, 8, 13), (64, 16, 8), (32, 32, 32), (64, 16, 32)]
+SHAPES = list(GPU_SHAPES)
+# the shapes this file began with come first and keep their parametrised ids
+assert SHAPES[:7] == [(8, 2, 2), (8, 8, 8), (16, 4, 31), (32, 8, 13), (64, 16, 8), (32, 32, 32), (64, 16, 32)]
+# K = 4 with 240 owned quads that do not exist; the largest K = 4 lattice; the largest two-image lattice (20
+# missing quads); K = 8 with one image, Ly = 2 and 496 missing quads
+MEASURED = [(64, 3, 43), (16, 32, 32), (8, 50, 51), (32, 2, 321)]
 DTAU, M2, LAM = 0.02, 0.5, 1.0
 SEEDS = [1234, 99, 0xDEADBEEF12345]
 
@@ -75,6 +80,7 @@ def _noisy_run(oracle_mod, shape):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_noiseless_bitwise_vs_oracle(gpu, oracle_mod, shape):
+    assert_shape(shape)
     phi0 = _starts(oracle_mod, shape)
     with _ens(shape, 3, C=0.0, seeds=SEEDS) as E:
         E.upload(phi0)
@@ -89,6 +95,7 @@ def test_noiseless_bitwise_vs_oracle(gpu, oracle_mod, shape):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_noisy_bitwise_vs_device_oracle(gpu, dev_oracle, shape):
+    assert_shape(shape)
     phi0 = _starts(dev_oracle, shape)
     got = _noisy_run(dev_oracle, shape)
     for r in range(3):
@@ -98,6 +105,7 @@ def test_noisy_bitwise_vs_device_oracle(gpu, dev_oracle, shape):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_noisy_within_tolerance_of_mathematical_oracle(gpu, oracle_mod, shape):
+    assert_shape(shape)
     phi0 = _starts(oracle_mod, shape)
     got = _noisy_run(oracle_mod, shape)
     k = 4
@@ -108,8 +116,9 @@ def test_noisy_within_tolerance_of_mathematical_oracle(gpu, oracle_mod, shape):
         assert np.all(err <= k * (PHI4_STEP_ATOL + PHI4_STEP_RTOL * np.abs(ref)))
 
 
-@pytest.mark.parametrize("shape", [(8, 8, 8), (32, 8, 13), (32, 32, 32)])
+@pytest.mark.parametrize("shape", [(8, 8, 8), (32, 8, 13), (32, 32, 32), (64, 3, 43), (8, 50, 51)])
 def test_bitwise_vs_single_context(gpu, shape):
+    assert_shape(shape)
     dt = [0.005, 0.01, 0.02, 0.03]
     m2 = [-0.5, 0.25, 0.5, 1.0]
     lam = [0.5, 1.0, 2.0, 4.0]
@@ -239,8 +248,9 @@ def _exact_sums(phi):
     return np.array(sums), np.array(bounds), float(np.abs(phi).max())
 
 
-@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32)])
+@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32)] + MEASURED)
 def test_series_and_moments(gpu, oracle_mod, shape):
+    assert_shape(shape)
     phi0 = _starts(oracle_mod, shape)
     with _ens(shape, 3, seeds=SEEDS) as E, _ens(shape, 3, seeds=SEEDS) as Ref:
         E.upload(phi0)
@@ -268,8 +278,8 @@ def test_series_and_moments(gpu, oracle_mod, shape):
         print(f"SUMS {shape} worst err/bound = {worst:.3e}", flush=True)
 
 
-def test_series_drops_the_incomplete_tail(gpu, oracle_mod):
-    shape = (16, 4, 31)
+def _incomplete_tail(oracle_mod, shape):
+    assert_shape(shape)
     phi0 = _starts(oracle_mod, shape)
     with _ens(shape, 3, seeds=SEEDS) as E, _ens(shape, 3, seeds=SEEDS) as Ref:
         E.upload(phi0)
@@ -286,6 +296,15 @@ def test_series_drops_the_incomplete_tail(gpu, oracle_mod):
         assert np.array_equal(E.download(), Ref.download())
         assert E.step(3, every=5).shape == (0, 3, 4)
         assert E.step(2) is None
+
+
+def test_series_drops_the_incomplete_tail(gpu, oracle_mod):
+    _incomplete_tail(oracle_mod, (16, 4, 31))
+
+
+@pytest.mark.parametrize("shape", MEASURED)
+def test_series_drops_the_incomplete_tail_at(gpu, oracle_mod, shape):
+    _incomplete_tail(oracle_mod, shape)
 
 
 def test_ranges_and_errors(gpu):

@@ -22,13 +22,22 @@ import math
 import numpy as np
 import pytest
 
+from test_phi4_ens_shapes import assert_shape
+
 pytestmark = pytest.mark.gpu
 
 LOOPS, NFR = 12, 40
 SEEDS = [99, 1234, 0xDEADBEEF12345]
 DTAU0 = [0.19, 0.01, 0.19]
 STEP0 = [0, 0, 2 ** 32 - 100]      # replica 2's counter carries into the high word during the run
-SHAPES = [(8, 2, 2), (16, 4, 31), (64, 16, 8), (32, 32, 32), (64, 16, 32)]
+SHAPES = [(8, 2, 2), (16, 4, 31), (64, 16, 8), (32, 32, 32), (64, 16, 32),
+          # K >= 2 with owned quads that do not exist (lanes that carry -inf quads and mp = 0 through the record),
+          # K = 4, K = 8 with two images at the LDS limit, the first one-image lattice, Ly = 2 at K = 8
+          (8, 17, 31), (64, 3, 43), (16, 32, 32), (8, 50, 51), (64, 11, 29), (32, 2, 321),
+          # the other ways the last j can end, per K and image count: inside a wave with every wave still holding
+          # a quad, and on a wave boundary with whole waves empty (test_phi4_ens_shapes.py)
+          (8, 20, 28), (8, 16, 34), (32, 4, 71), (16, 20, 28), (32, 12, 47), (16, 16, 71), (64, 12, 29)]
+MEASURED = [(64, 3, 43), (16, 32, 32), (8, 50, 51), (32, 2, 321)]
 
 _cache = {}
 
@@ -94,7 +103,9 @@ def _check(E, st, dt, r, ref, tag=""):
 @pytest.mark.parametrize("shape", SHAPES)
 def test_frames_bitwise_vs_single_context(gpu, shape):
     """One wave; K = 1 with a partial wave and two images; K = 2; K = 8 with one
-    image, where the rollback rewrites the image behind the two-barrier step."""
+    image, where the rollback rewrites the image behind the two-barrier step;
+    the work-group shapes of test_phi4_ens_shapes.GPU_SHAPES beyond those."""
+    assert_shape(shape)
     refs = [_ref(shape, r) for r in range(3)]
     assert refs[0]["stable"].any() and not refs[0]["stable"].all(), refs[0]["stable"]
     assert refs[1]["stable"].all()            # Δτ₀ = 0.01 never rolls back: three Δτ / 0.95 in 40 frames
@@ -111,8 +122,9 @@ def test_frames_bitwise_vs_single_context(gpu, shape):
         assert NFR * LOOPS + 2 * NFR <= p["steps"] <= 3 * NFR * LOOPS
 
 
-@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32)])
+@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32), (64, 3, 43), (64, 11, 29)])
 def test_split_calls_and_raw_steps_between(gpu, shape):
+    assert_shape(shape)
     refs = [_ref(shape, r) for r in range(3)]
     assert refs[0]["stable"].any() and not refs[0]["stable"].all()
     with _recipe(shape) as E:
@@ -183,6 +195,44 @@ def test_rule_only_rollback_vs_oracle(gpu, oracle_mod, shape):
         assert E.perf()["steps"] == n + LOOPS                 # the rejected frame stopped at the firing step
 
 
+@pytest.mark.parametrize("shape", [(16, 4, 31), (8, 17, 31), (64, 3, 43)])
+def test_negative_maximum_vs_oracle(gpu, oracle_mod, shape):
+    """A field whose maximum is negative: the step's record takes atomic maxima
+    of ordered keys over LDS words that start at 0, the wave's running maximum
+    starts at -inf, and a lane without a quad carries mp = 0, above every site
+    here.  K = 1 with a partial wave, K = 2 and K = 4 with waves that have such
+    lanes.  C = 0, so the oracle's frame (oracle.phi4_frame_stab) is the
+    reference bit for bit: two frames, the second from the carried negative T;
+    a mixed-sign replica beside it in the same launch is checked the same way."""
+    assert_shape(shape)
+    h = 0.01
+    p = [oracle_mod.phi4_params(shape, h, 1.0, 1.0, s, C=0.0) for s in (1234, 99)]
+    phi = [-2.0 - np.abs(oracle_mod.phi4_init(p[0], 0.3)), oracle_mod.phi4_init(p[1], 0.3)]
+    assert phi[0].dtype == np.float32 and phi[0].max() < 0 and phi[1].max() > 0 > phi[1].min()
+    T = [float(f.max()) for f in phi]                         # a replica's first frame takes T, V from its start field
+    V = [float(np.abs(f).max()) for f in phi]
+    with _ens(shape, 2, dtau=h, C=0.0, seeds=[1234, 99]) as E:
+        E.upload(np.stack(phi))
+        for frame in range(2):
+            ok = E.run_frame()
+            st = E.stability()
+            got = E.download()
+            assert list(E.dtau) == [h, h] and not E.flags().any()
+            for r in range(2):
+                out, M, D, A, fired, T1, V1 = oracle_mod.phi4_frame_stab(p[r], phi[r], LOOPS, frame * LOOPS, T[r], V[r])
+                tag = (shape, frame, r)
+                assert fired < 0, tag                         # Δτ = 0.01 is far below the Euler limit
+                if r == 0:
+                    assert np.all(M < 0) and T1 < 0 and out.max() < 0, tag      # negative through all 12 steps
+                assert bool(ok[r]) and st["fired"][r] == -1, tag
+                assert st["T"][r] == T1 and st["V"][r] == V1, (tag, st["T"][r], T1, st["V"][r], V1)
+                for k, ref in (("M", M), ("D", D), ("A", A)):
+                    assert np.array_equal(st[k][r], ref), (tag, k, st[k][r], ref)
+                assert np.array_equal(got[r], out), tag
+                phi[r], T[r], V[r] = out, T1, V1
+        assert list(E.step_counter) == [2 * LOOPS, 2 * LOOPS]
+
+
 def test_adapt_dtau_off(gpu):
     shape, nfr = (16, 4, 31), 20
     refs = [_ref(shape, r, adapt=False, nfr=nfr) for r in range(3)]
@@ -249,8 +299,9 @@ def _exact_sums(phi):
             np.array([2 * t.size * u * math.fsum(np.abs(t)) for t in terms]))
 
 
-@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32)])
+@pytest.mark.parametrize("shape", [(16, 4, 31), (32, 32, 32)] + MEASURED)
 def test_measure_rows(gpu, shape):
+    assert_shape(shape)
     names = ("S1", "S2", "S4", "NN")
     with _recipe(shape) as E, _recipe(shape) as Tw:
         st, dt, ser = E.run_frames(NFR, measure=True)

@@ -9,7 +9,7 @@ import pytest
 ENS_SYMBOLS = ["sq_phi4_ens_create", "sq_phi4_ens_destroy", "sq_phi4_ens_upload", "sq_phi4_ens_download",
                "sq_phi4_ens_init_field", "sq_phi4_ens_set_params", "sq_phi4_ens_get_params", "sq_phi4_ens_get_step",
                "sq_phi4_ens_set_step", "sq_phi4_ens_step", "sq_phi4_ens_moments", "sq_phi4_ens_flags",
-               "sq_phi4_ens_perf"]
+               "sq_phi4_ens_perf", "sq_phi4_ens_shape_info"]
 
 
 def _create(sqlib, nrep=4, shape=(8, 8, 8), **kw):

@@ -1,0 +1,160 @@
+"""Every work-group shape of the phi^4 ensemble kernels, without a GPU.
+
+sq_phi4_ens_shape_info (Phi4Ensemble.shape_info) reports, from the function
+the launchers call, how a lattice is dealt to its work-group: K float4 quads
+per lane, T lanes, and per launch the LDS images and dynamic LDS bytes.  This
+file calls it for every legal (Lx, Ly, Lz), checks the invariants the kernels
+rely on, and asserts that the GPU suites' shape list (GPU_SHAPES, run by
+test_gpu_phi4_ens.py, test_gpu_phi4_ens_frames.py and
+test_gpu_phi4_ens_shapes.py) holds a lattice of every class that exists:
+
+    class = (K, images of the step launch, images of the frames launch,
+             K T == Q, the last j's boundary lies inside a wave,
+             a whole wave has no quad at the last j)
+
+with Q = sites / 4 the lattice's quads.  Lane t owns quads t + j T, j < K; the
+quads of j = K - 1 exist for t < n_last = Q - (K - 1) T only, so K T - Q owned
+quads do not exist: n_last % 64 != 0 puts the boundary inside a wave, and
+T - n_last >= 64 leaves whole waves without one.  If a threshold of
+phi4_ens_shape moves, the coverage test names the class no GPU test runs.
+"""
+import pytest
+
+LDS_LIMIT = 160 * 1024
+# sq_phi4_ens.h: per wave 4 doubles and one float for 16 waves; the frames launch adds three step records
+# (u64 key, u32 max) and the start field's two maxima, padded to 8 bytes
+SCRATCH = 16 * 4 * 8 + 16 * 4
+FRAME_SCRATCH = SCRATCH + 3 * 8 + 3 * 4 + 2 * 4 + 4
+MAX_SITES = 32768
+LX = (8, 16, 32, 64)
+
+# The shapes the ensemble's GPU tests run: (K, T, images of the step launch, images of the frames launch).
+GPU_SHAPES = {
+    (8, 2, 2): (1, 64, 2, 2),          # one wave, 56 of its lanes without a quad; y and z neighbours coincide
+    (8, 8, 8): (1, 128, 2, 2),
+    (16, 4, 31): (1, 512, 2, 2),       # partial last wave
+    (32, 8, 13): (1, 832, 2, 2),
+    (64, 16, 8): (2, 1024, 2, 2),
+    (32, 32, 32): (8, 1024, 1, 1),
+    (64, 16, 32): (8, 1024, 1, 1),
+    (8, 17, 31): (2, 576, 2, 2),       # 98 missing quads: the last j ends mid-wave, one wave has none
+    (16, 24, 24): (4, 576, 2, 2),      # exact fit
+    (64, 3, 43): (4, 576, 2, 2),       # 240 missing quads: mid-wave and three empty waves
+    (16, 32, 32): (4, 1024, 2, 2),     # the largest K = 4 lattice
+    (32, 24, 24): (8, 576, 2, 2),      # K = 8 with two images
+    (8, 50, 51): (8, 640, 2, 2),       # the largest two-image lattice, 20 missing quads
+    (64, 11, 29): (8, 640, 1, 1),      # the first one-image lattice, 16 missing quads
+    (32, 2, 321): (8, 704, 1, 1),      # Ly = 2, 496 missing quads
+    (8, 2, 2048): (8, 1024, 1, 1),     # a plane of four quads
+    (64, 256, 2): (8, 1024, 1, 1),     # Lz = 2 at full size
+    # the classes the coverage test named beyond those: a boundary inside a wave and no empty wave (32 missing
+    # quads), whole waves only (64 missing), at the K and image counts where the list had neither
+    (8, 20, 28): (2, 576, 2, 2),       # 32 missing
+    (8, 16, 34): (2, 576, 2, 2),       # 64 missing
+    (32, 4, 71): (4, 576, 2, 2),       # 32 missing
+    (16, 20, 28): (4, 576, 2, 2),      # 64 missing
+    (32, 12, 47): (8, 576, 2, 2),      # 96 missing: mid-wave and one empty wave, two images
+    (16, 16, 71): (8, 576, 2, 2),      # 64 missing, two images
+    (64, 12, 29): (8, 704, 1, 1),      # 64 missing, one image
+}
+
+
+def shape_info(shape):
+    from stochquant_amd import Phi4Ensemble
+    return Phi4Ensemble.shape_info(shape)
+
+
+def shape_class(shape, info=None):
+    """The class of the module docstring, from what shape_info reports."""
+    i = shape_info(shape) if info is None else info
+    Q = shape[0] * shape[1] * shape[2] // 4
+    K, T = i["K"], i["T"]
+    n_last = Q - (K - 1) * T
+    return (K, i["images"], i["frames_images"], K * T == Q, n_last % 64 != 0, T - n_last >= 64)
+
+
+def assert_shape(shape):
+    """A GPU test's gate: the library still gives `shape` the work-group shape the test was written for."""
+    i = shape_info(shape)
+    assert (i["K"], i["T"], i["images"], i["frames_images"]) == GPU_SHAPES[tuple(shape)], (shape, i)
+    return i
+
+
+def legal_shapes():
+    for Lx in LX:
+        for Ly in range(2, MAX_SITES // (2 * Lx) + 1):
+            for Lz in range(2, MAX_SITES // (Lx * Ly) + 1):
+                yield (Lx, Ly, Lz)
+
+
+@pytest.fixture(scope="module")
+def infos(sqlib):
+    return {s: shape_info(s) for s in legal_shapes()}
+
+
+def test_every_legal_shape(infos):
+    assert len(infos) == 45843
+    for (Lx, Ly, Lz), i in infos.items():
+        tag = ((Lx, Ly, Lz), i)
+        sites = Lx * Ly * Lz
+        Q = sites // 4
+        K, T = i["K"], i["T"]
+        assert K in (1, 2, 4, 8), tag
+        assert T % 64 == 0 and 64 <= T <= 1024, tag
+        assert K * T >= Q and (K - 1) * T < Q, tag        # every j has a quad somewhere in the block
+        assert T <= (Q + 63) // 64 * 64, tag
+        assert T - 64 < Q, tag                            # every wave owns an existing quad at j = 0
+        assert i["lds_limit"] == LDS_LIMIT, tag
+        for images, nbytes, scratch in ((i["images"], i["lds_bytes"], SCRATCH),
+                                        (i["frames_images"], i["frames_lds_bytes"], FRAME_SCRATCH)):
+            assert images in (1, 2), tag
+            assert nbytes == images * 4 * sites + scratch <= LDS_LIMIT, tag
+            assert (images == 2) == (2 * 4 * sites + scratch <= LDS_LIMIT), tag   # two images exactly when they fit
+        assert i["moments_lds_bytes"] == 4 * sites + SCRATCH <= LDS_LIMIT, tag
+
+
+@pytest.mark.parametrize("shape", [(4, 8, 8), (12, 8, 8), (24, 8, 8), (128, 8, 8), (0, 8, 8), (-8, 8, 8), (8, 1, 8),
+                                   (8, 8, 1), (8, 0, 8), (8, 8, -2), (8, 17, 241), (8, 2, 2049), (8, 2049, 2), (16, 2, 1025),
+                                   (32, 32, 33), (64, 2, 257), (8, 4097, 1), (8, 65536, 65536), (64, 32768, 32768)])
+def test_shapes_just_outside_are_refused(sqlib, shape):
+    import ctypes
+    from stochquant_amd import StochQuantError
+    with pytest.raises(StochQuantError) as ei:
+        shape_info(shape)
+    assert ei.value.code == -1 and str(ei.value) != ""
+    out = (ctypes.c_int * 8)()
+    assert sqlib.sq_phi4_ens_shape_info(None, out) == -1
+    assert sqlib.sq_phi4_ens_shape_info((ctypes.c_int * 3)(8, 8, 8), None) == -1
+
+
+def test_refusals_are_those_of_create(sqlib):
+    """The query and sq_phi4_ens_create draw the same line: create answers SQ_E_ARG
+    exactly where the query does (elsewhere it goes on to look for a device)."""
+    from test_phi4_ens_boundary import _create
+    for shape in [(8, 2, 2), (8, 2, 2048), (64, 256, 2), (16, 2, 1024), (8, 2, 2049), (16, 2, 1025), (8, 1, 8),
+                  (8, 8, 1), (12, 8, 8), (128, 2, 2), (32, 32, 33)]:
+        try:
+            shape_info(shape)
+            refused = False
+        except Exception:
+            refused = True
+        rc, _ = _create(sqlib, shape=shape)
+        assert (rc == -1) == refused, (shape, rc)
+
+
+def test_gpu_shape_list_covers_every_class(infos):
+    have = {}
+    for s, want in GPU_SHAPES.items():
+        i = infos[s]
+        assert (i["K"], i["T"], i["images"], i["frames_images"]) == want, (s, i)
+        have.setdefault(shape_class(s, i), s)
+    missing = {}
+    for s, i in infos.items():
+        c = shape_class(s, i)
+        if c not in have:
+            missing.setdefault(c, s)
+    names = ("K", "images", "frames images", "K T == Q", "boundary inside a wave", "a wave without a last-j quad")
+    assert not missing, "no GPU test runs: " + "; ".join(
+        ", ".join(f"{n} = {v}" for n, v in zip(names, c)) + f" (e.g. {s[0]} x {s[1]} x {s[2]})"
+        for c, s in sorted(missing.items()))
+    assert {s[0] for s in GPU_SHAPES} == set(LX)
