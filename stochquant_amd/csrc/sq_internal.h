@@ -6,6 +6,8 @@
 
 #include <string>
 
+#include "sq_noise_consts.h"
+
 namespace sq {
 
 // Sets the thread-local message returned by sq_last_error(); returns code.
@@ -79,7 +81,10 @@ struct Phi4StepArgs {
     int fin;                  // the input field is known finite (every plane has been through the
                               // guard): the guard then runs only where |phi'| >= clampv
     uint32_t k0, k1, s_lo, s_hi;
-    int *flag;                // guard flag: set to 1 when a site was clamped / NaN (nullable: frames only)
+    // the fused kernels: the wave-uniform noise words of steps s and s+1
+    // (phi4_noise_consts of k0, k1 and the step; set wherever s_lo / s_hi are)
+    Phi4NoiseConsts nw0, nw1;
+    int *flag;               // guard flag: set to 1 when a site was clamped / NaN (nullable: frames only)
     // stability records of this launch's step(s) (nullable; frames only): for
     // step k of the launch, kStabSlots words each at st_md + k*kStabSlots
     // (u64 max of ord(max phi') << 32 | bits(drift increment there)) and
@@ -93,7 +98,7 @@ struct Phi4StepArgs {
     // by the frame instances at launch start (FrameCtl::coef; the controller
     // kernel of the previous frame may have changed Δτ)
     const float *dcoef;
-    int prio;  // fused kernels: wave priority by march progress (prio_by_progress)
+    int prio;  // fused kernels: wave priority by march progress (PrioQ::set)
     // fused kernels (nullable): per block b, the constant 100 MHz clock
     // (s_memrealtime) at its start and end, stamps[2b], stamps[2b+1]
     unsigned long long *stamps;

@@ -859,7 +859,7 @@ __global__ __launch_bounds__(256) void phi4_step_kernel(const Phi4StepArgs A0) {
 // stamps: ends 20..36 us at 256^3, 19-20 us alone).  A block that is behind
 // gets the higher priority: 3 in its first quarter of planes, down to 0 in
 // its last (4 levels beat 2: 3 then 0 by halves, 512^3 139-140 vs 136-137
-// us/step).  q = quarter (0..3), wave-uniform.
+// us/step): PrioQ::set, wave-uniform.
 // Block stamps (Phi4StepArgs::stamps): [2b, 2b+1] the constant 100 MHz clock
 // (s_memrealtime) at the block's start and end, [2 nb + 2b, 2 nb + 2b + 1] the
 // shader-clock counter (s_memtime) at the same two points: their ratio is the
@@ -884,17 +884,16 @@ struct PrioQ {
     int t0, t1, t2;
     __device__ __forceinline__ PrioQ(int z0, int span)
         : t0(z0 - 1 + (span + 3) / 4), t1(z0 - 1 + (2 * span + 3) / 4), t2(z0 - 1 + (3 * span + 3) / 4) {}
-    __device__ __forceinline__ int q(int p) const { return (p >= t0) + (p >= t1) + (p >= t2); }
-};
-
-__device__ __forceinline__ void prio_by_progress(int q) {
-    switch (q) {
-    case 0: __builtin_amdgcn_s_setprio(3); break;
-    case 1: __builtin_amdgcn_s_setprio(2); break;
-    case 2: __builtin_amdgcn_s_setprio(1); break;
-    default: __builtin_amdgcn_s_setprio(0); break;
+    // Wave priority 3 - quarter, by compares and branches on
+    // the scalar unit (t0 <= t1 <= t2): the quarter as a number, the sum of the
+    // three compares, went through VGPRs, 5 VALU per unrolled march loop.
+    __device__ __forceinline__ void set(int p) const {
+        if (p < t0) __builtin_amdgcn_s_setprio(3);
+        else if (p < t1) __builtin_amdgcn_s_setprio(2);
+        else if (p < t2) __builtin_amdgcn_s_setprio(1);
+        else __builtin_amdgcn_s_setprio(0);
     }
-}
+};
 
 // A fused launch's block -> (y-band, x-segment, z-chunk).  Blocks are dealt
 // XCD-contiguously (consecutive ids round-robin over the 8 XCDs, so the
@@ -985,6 +984,67 @@ __device__ __forceinline__ f32x4n tb_noise(const Phi4StepArgs &A, uint32_t qz, u
     return xi;
 }
 
+// The fused kernels' form of the same evaluation, from the launch's noise words
+// (Phi4NoiseConsts, sq_noise_consts.h: nothing wave-uniform is derived per
+// plane, so no v_readfirstlane and no scalar products in the march) and split
+// at round 1's xors.  A quad's work up to there -- hi / lo of round 1's M1
+// product and round 0's lo(M0 quad) -- depends on the step only through
+// a0 = step_hi ^ k1, so an output row wave keeps it from step s at plane p for
+// step s+1 at the same sites one iteration later.  Only the pair with
+// s_lo = 0xFFFFFFFF has two a0 (TbCtx::da != 0): there the kept prefix is
+// re-keyed once step s is done with it -- n2 = hi(p0) ^ a0 recovered from
+// lo(p1) = M1 n2 mod 2^32 (M1 is odd, so invertible) and round 1's product
+// redone with step s+1's a0 (noise_rekey) -- from the lane's registers alone
+// and in place, behind a scalar branch no other launch takes.
+struct NoisePre {
+    uint32_t h1, l1, n3;
+};
+
+__device__ __forceinline__ NoisePre noise_prefix(uint32_t quad, uint32_t a0) {
+    const uint64_t p0 = (uint64_t)kPhiloxM0 * quad;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ a0;
+    const uint64_t p1 = (uint64_t)kPhiloxM1 * n2;
+    return NoisePre{(uint32_t)(p1 >> 32), (uint32_t)p1, (uint32_t)p0};
+}
+
+__device__ __forceinline__ NoisePre noise_rekey(const NoisePre &q, uint32_t da) {  // da = a0 ^ a0'
+    const uint32_t n2 = q.l1 * kPhiloxM1Inv;
+    const uint64_t p1 = (uint64_t)kPhiloxM1 * (n2 ^ da);
+    return NoisePre{(uint32_t)(p1 >> 32), (uint32_t)p1, q.n3};
+}
+
+// Rounds 1 (its xors) .. 9 and the Box-Muller pairs: philox_field's operations
+// in philox_field's order, so the same normals bit for bit.
+template <bool NZ>
+__device__ __forceinline__ f32x4n tb_noise(const Phi4StepArgs &A, const NoisePre &q, const Phi4NoiseConsts &W) {
+    f32x4n xi;
+    if constexpr (NZ) {
+        uint32_t k0 = A.k0 + 2u * kPhiloxW0, k1 = A.k1 + 2u * kPhiloxW1;
+        u32x4 c;
+        {  // round 1's state {hi(p1) ^ b0, lo(p1), b2 ^ n3, u3} through round 2 (word 3 still uniform: d2)
+            const uint64_t p0 = (uint64_t)kPhiloxM0 * (q.h1 ^ W.b0);
+            const uint64_t p1 = (uint64_t)kPhiloxM1 * (W.b2 ^ q.n3);
+            const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), q.l1, k0, 0x96);
+            c = u32x4{n0, (uint32_t)p1, (uint32_t)(p0 >> 32) ^ W.d2, (uint32_t)p0};
+        }
+#pragma unroll
+        for (int rnd = 3; rnd < 10; ++rnd) {
+            k0 += kPhiloxW0;
+            k1 += kPhiloxW1;
+            const uint64_t p0 = (uint64_t)kPhiloxM0 * c.x;
+            const uint64_t p1 = (uint64_t)kPhiloxM1 * c.z;
+            const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c.y, k0, 0x96);
+            const uint32_t m2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c.w, k1, 0x96);
+            c = u32x4{n0, (uint32_t)p1, m2, (uint32_t)p0};
+        }
+        box_muller_q(c.x, c.y, xi.a, xi.b);  // scaled by 1/sqrt(2 ln 2); A.sigq carries the factor
+        box_muller_q(c.z, c.w, xi.c, xi.d);
+    } else {
+        xi = f32x4n{0.f, 0.f, 0.f, 0.f};
+    }
+    return xi;
+}
+
 // One plane of a row wave's inputs: its row and the row's two y-neighbours.
 // The x-halo wave keeps the centre values of its sites in row.x, so the two
 // roles share one register queue.
@@ -1004,8 +1064,11 @@ struct TbCtx {
     // segment (lane 0 left, lane 63 right).  x-halo wave lanes (sharing the
     // registers): voff the site, vm / vp its y-neighbours, vex / vx2 its x-1 / x+1.
     uint32_t voff, vm, vp, vex, vx2, qoff;
-    uint32_t slo, shi, slo1, shi1;
-    uint32_t qwrap;      // Lz_global * plane / 4: where the Philox quad base wraps
+    Phi4NoiseConsts nw0, nw1;  // the noise words of steps s and s+1 (wave-uniform)
+    // a0 of step s ^ a0 of step s+1: 0 unless s_lo = 0xFFFFFFFF; then step s's
+    // kept NoisePre is re-keyed for step s+1 (noise_rekey)
+    uint32_t da;
+    uint32_t qwrap;     // Lz_global * plane / 4: where the Philox quad base wraps
     f32x2 m2v;           // {m2, m2}, pinned in VGPRs (site_update4)
     int swrap_at;        // WH, periodic: the plane p at which plane p+1's input wraps to local 0
     int z0, z1, w, lane;
@@ -1026,6 +1089,12 @@ struct TbRun {
     uint32_t snext, scur;
     uint32_t qz, qzm;
 };
+
+__device__ __forceinline__ void tb_noise_words(TbCtx &K, const Phi4NoiseConsts &w0, const Phi4NoiseConsts &w1) {
+    K.nw0 = w0;
+    K.nw1 = w1;
+    K.da = w0.a0 ^ w1.a0;
+}
 
 __device__ __forceinline__ float tb_site(float phi, float xm, float xp, float ym, float yp, float zm, float zp,
                                          float xi, const Phi4StepArgs &A, bool nz) {
@@ -1063,10 +1132,11 @@ __device__ __forceinline__ void tb_wait_nbrs(const int *prog, int w, int need) {
     }
 }
 
-template <bool NZ, bool WIDE, bool FR, bool WH, int J, bool P2 = false, int LAUX = 0, bool STG = false>
+template <bool NZ, bool WIDE, bool FR, bool WH, int J, bool P2 = false, int LAUX = 0, bool STG = false, bool CY = true>
 __device__ __forceinline__ void tb_plane(const Phi4StepArgs &A, const TbCtx &K, TbRun &R, int p, const TbIn &I0,
                                          const TbIn &I1, TbIn &I2, const float4 &T0, const float4 &T1, float4 &T2,
-                                         float4 (*lds)[kTbWaves][64], float (*tx)[kTbWaves][2], FrameAcc &f1,
+                                         const NoisePre &Q1, NoisePre &Q2, float4 (*lds)[kTbWaves][64],
+                                         float (*tx)[kTbWaves][2], FrameAcc &f1,
                                          FrameAcc &f2, float *bmx, int *prog = nullptr) {
     constexpr int sl = J, sp = (J + 2) % 3;  // slots of planes p and p-1
     __amdgpu_buffer_rsrc_t rs, rc;
@@ -1088,7 +1158,8 @@ __device__ __forceinline__ void tb_plane(const Phi4StepArgs &A, const TbCtx &K, 
         I2.hp = bload4<LAUX>(rs, K.vp, ss);
         float ex = 0.f;
         if constexpr (WIDE) ex = bload1(rc, K.vex, sc);
-        const f32x4n xa = tb_noise<NZ>(A, R.qz, K.qoff, K.slo, K.shi);
+        const NoisePre qa = noise_prefix(R.qz + K.qoff, K.nw0.a0);
+        const f32x4n xa = tb_noise<NZ>(A, qa, K.nw0);
         float lft, rgt;
         if constexpr (WIDE) {
             lft = from_left_lane_or(I1.row.w, ex);
@@ -1111,6 +1182,10 @@ __device__ __forceinline__ void tb_plane(const Phi4StepArgs &A, const TbCtx &K, 
                     (f32x4v){I2.row.x, I2.row.y, I2.row.z, I2.row.w},
                     reinterpret_cast<f32x4v *>(reinterpret_cast<char *>(A.snap) + (size_t)(p + 1) * K.pbytes + K.voff));
         }
+        if constexpr (CY) {  // kept for step s+1 at these sites, one iteration on
+            Q2 = qa;
+            if (K.da != 0u) Q2 = noise_rekey(Q2, K.da);
+        }
         if constexpr (P2) tb_wait_nbrs(prog, K.w, p - 1);
         lds[sl][K.w][K.lane] = T2;
     } else {
@@ -1118,7 +1193,7 @@ __device__ __forceinline__ void tb_plane(const Phi4StepArgs &A, const TbCtx &K, 
         I2.row.x = bload1(rs, K.voff, ss);
         const float xm = bload1(rc, K.vex, sc), xp = bload1(rc, K.vx2, sc), ym = bload1(rc, K.vm, sc),
                     yp = bload1(rc, K.vp, sc);
-        const f32x4n n = tb_noise<NZ>(A, R.qz, K.qoff, K.slo, K.shi);
+        const f32x4n n = tb_noise<NZ>(A, noise_prefix(R.qz + K.qoff, K.nw0.a0), K.nw0);
         // lanes 0..7 hold x0-1 (component 3 of its quad), 8..15 x0+256 (component 0)
         const float xi = K.lane >= 8 ? n.a : n.d;
         const float t = tb_site(I1.row.x, xm, xp, ym, yp, I0.row.x, I2.row.x, xi, A, NZ);
@@ -1130,7 +1205,13 @@ __device__ __forceinline__ void tb_plane(const Phi4StepArgs &A, const TbCtx &K, 
         __syncthreads();
     }
     if (K.outw && p > K.z0) {
-        const f32x4n xb = tb_noise<NZ>(A, R.qzm, K.qoff, K.slo1, K.shi1);
+        NoisePre qb;
+        if constexpr (CY) {
+            qb = Q1;  // plane p-1's sites: what step s left one iteration ago
+        } else {
+            qb = noise_prefix(R.qzm + K.qoff, K.nw1.a0);
+        }
+        const f32x4n xb = tb_noise<NZ>(A, qb, K.nw1);
         const float4 up = lds[sp][K.w - 1][K.lane], dn = lds[sp][K.w + 1][K.lane];
         float lft, rgt;
         if constexpr (WIDE) {
@@ -1209,11 +1290,7 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2_kernel(const Phi4StepArg
     asm volatile("" : "+v"(K.m2v));  // opaque: kept in VGPRs, not rematerialised from SGPRs per update
     // periodic: plane p+1 = nz is local plane 0 (tb_pidx); p never reaches it otherwise
     K.swrap_at = A.periodic ? A.nz - 2 : INT_MIN;  // slabs: p < 0 in ghost zones, never INT_MIN
-    const unsigned long long s0 = ((unsigned long long)A.s_hi << 32) | A.s_lo, s1 = s0 + 1;
-    K.slo = (uint32_t)s0;
-    K.shi = (uint32_t)(s0 >> 32);
-    K.slo1 = (uint32_t)s1;
-    K.shi1 = (uint32_t)(s1 >> 32);
+    tb_noise_words(K, A.nw0, A.nw1);
     const int xl = (x0 == 0 ? Lx : x0) - 1, xr = x0 + 256 == Lx ? 0 : x0 + 256;  // just outside the segment
     auto wrapy = [Ly](int y) { return y < 0 ? y + Ly : (y >= Ly ? y - Ly : y); };
     if (!WIDE || K.w < kTbWaves) {
@@ -1274,6 +1351,7 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2_kernel(const Phi4StepArg
         }
     }
     float4 T0 = make_float4(0.f, 0.f, 0.f, 0.f), T1 = T0, T2 = T0;
+    NoisePre Q0{0u, 0u, 0u}, Q1 = Q0, Q2 = Q0;  // step s's noise prefixes, rotating as T
     FrameAcc f1 = frame_acc(), f2 = frame_acc();  // steps s and s+1
     __shared__ float bmx[2];                        // the block's running maxima of both records (frame_sites)
     __shared__ unsigned long long fk[2];            // frame_flush2's block maxima
@@ -1296,15 +1374,39 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2_kernel(const Phi4StepArg
         if (threadIdx.x < kTbWaves) prog[threadIdx.x] = K.z0 - 2;
         __syncthreads();
     }
-    // three-plane queues unrolled three ways so no rotation moves are emitted
+    // three-plane queues unrolled three ways so no rotation moves are emitted.
+    // CY: step s+1 starts from step s's carried noise prefix where the queue's
+    // six live VGPRs fit the instance's budget -- 256-site rows without frame
+    // records (72 of 96); the frame instances (80 VGPRs for 6 waves per SIMD)
+    // and the wide rows would spill for it.
+    constexpr bool CY = !WIDE && !FR;
     const PrioQ pq(K.z0, z1 - K.z0 + 2);
-    for (int p = K.z0 - 1; p <= z1; p += 3) {
-        if (A.prio) prio_by_progress(pq.q(p));
-        tb_plane<NZ, WIDE, FR, WH, 0, P2>(A, K, R, p, I0, I1, I2, T0, T1, T2, lds, tx, f1, f2, bmx, prog);
-        if (p + 1 > z1) break;
-        tb_plane<NZ, WIDE, FR, WH, 1, P2>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, lds, tx, f1, f2, bmx, prog);
-        if (p + 2 > z1) break;
-        tb_plane<NZ, WIDE, FR, WH, 2, P2>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, lds, tx, f1, f2, bmx, prog);
+    if constexpr (CY) {
+        // one exit, at the loop's end: with the carried prefixes, early exits
+        // by break made the compiler keep the plane offsets in VGPRs and issue
+        // every load of the march through a readfirstlane loop
+        for (int p = K.z0 - 1; p <= z1; p += 3) {
+            if (A.prio) pq.set(p);
+            tb_plane<NZ, WIDE, FR, WH, 0, P2>(A, K, R, p, I0, I1, I2, T0, T1, T2, Q1, Q2, lds, tx, f1, f2, bmx, prog);
+            if (p + 1 <= z1) {
+                tb_plane<NZ, WIDE, FR, WH, 1, P2>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, Q2, Q0, lds, tx, f1, f2, bmx, prog);
+                if (p + 2 <= z1)
+                    tb_plane<NZ, WIDE, FR, WH, 2, P2>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, Q0, Q1, lds, tx, f1, f2, bmx,
+                                                      prog);
+            }
+        }
+    } else {  // (the nested form costs these instances registers: the frame ones would spill)
+        for (int p = K.z0 - 1; p <= z1; p += 3) {
+            if (A.prio) pq.set(p);
+            tb_plane<NZ, WIDE, FR, WH, 0, P2, 0, false, false>(A, K, R, p, I0, I1, I2, T0, T1, T2, Q1, Q2, lds, tx, f1, f2, bmx,
+                                                               prog);
+            if (p + 1 > z1) break;
+            tb_plane<NZ, WIDE, FR, WH, 1, P2, 0, false, false>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, Q2, Q0, lds, tx, f1, f2,
+                                                               bmx, prog);
+            if (p + 2 > z1) break;
+            tb_plane<NZ, WIDE, FR, WH, 2, P2, 0, false, false>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, Q0, Q1, lds, tx, f1, f2,
+                                                               bmx, prog);
+        }
     }
     if constexpr (FR) frame_flush2(A, f1, f2, fk, fa);  // step s's records, then s+1's
     block_end_stamp(A);
@@ -1353,10 +1455,10 @@ __device__ __forceinline__ void tp_advance(const Phi4StepArgs &A, const TbCtx &K
 }
 
 // One plane iteration of a row wave.
-template <bool NZ, bool WIDE, bool FR, bool WH, int J>
+template <bool NZ, bool WIDE, bool FR, bool WH, int J, bool CY>
 __device__ __forceinline__ void tp_row(const Phi4StepArgs &A, const TbCtx &K, TpRun &R, int k, bool xrow,
-                                       uint32_t vxr, int xslot, float4 (&I)[4], float4 (&T)[4], float4 (&X)[2],
-                                       float (&E)[2], float4 (*in_lds)[kTpRows][64], float4 (*t_lds)[kTbWaves][64],
+                                       uint32_t vxr, int xslot, float4 (&I)[4], float4 (&T)[4], NoisePre (&Q)[4],
+                                       float4 (&X)[2], float (&E)[2], float4 (*in_lds)[kTpRows][64], float4 (*t_lds)[kTbWaves][64],
                                        float (*tx)[kTbWaves][2], FrameAcc &f1, FrameAcc &f2, float *bmx) {
     constexpr int im = J, ic = (J + 1) & 3, ip = (J + 2) & 3, in2 = (J + 3) & 3;  // planes k-1, k, k+1, k+2
     constexpr int tc = J, tm = (J + 3) & 3, tmm = (J + 2) & 3;                    // T(k), T(k-1), T(k-2)
@@ -1390,7 +1492,8 @@ __device__ __forceinline__ void tp_row(const Phi4StepArgs &A, const TbCtx &K, Tp
         bstore4<2>(plane_rsrc(A.snap, k + 1, K.plane, K.pbytes), sv ? K.voff : kTpOob, I[ip]);
     }
     // 3. A: step s at plane k
-    const f32x4n xa = tb_noise<NZ>(A, R.qz, K.qoff, K.slo, K.shi);
+    const NoisePre qa = noise_prefix(R.qz + K.qoff, K.nw0.a0);
+    const f32x4n xa = tb_noise<NZ>(A, qa, K.nw0);
     const float4 up = in_lds[sc][K.w][K.lane], dn = in_lds[sc][K.w + 2][K.lane];
     float lft, rgt;
     if constexpr (WIDE) {
@@ -1405,13 +1508,23 @@ __device__ __forceinline__ void tp_row(const Phi4StepArgs &A, const TbCtx &K, Tp
     if constexpr (FR) {  // own rows and planes only, as phi4_tb2_kernel
         if (K.outw && k >= K.z0 && k < K.z1) frame_sites<NZ, true>(A, f1, T[tc], I[ic], xa, bmx, true, mp1);
     }
+    if constexpr (CY) {  // kept for step s+1 at these sites, one iteration on
+        Q[tc] = qa;
+        if (K.da != 0u) Q[tc] = noise_rekey(Q[tc], K.da);
+    }
     t_lds[sc][K.w][K.lane] = T[tc];
     // 4. B: step s+1 at plane k-1 from T(k-2), T(k-1), T(k) and T(k-1)'s
     //    y-neighbours, published in iteration k-1
     const bool bw = K.outw && k > K.z0;
     float4 o = T[tc];  // stored at an out-of-range offset unless bw
     if (bw) {
-        const f32x4n xb = tb_noise<NZ>(A, R.qzm, K.qoff, K.slo1, K.shi1);
+        NoisePre qb;  // plane k-1's sites: the prefix step s left one iteration ago
+        if constexpr (CY) {
+            qb = Q[tm];
+        } else {
+            qb = noise_prefix(R.qzm + K.qoff, K.nw1.a0);
+        }
+        const f32x4n xb = tb_noise<NZ>(A, qb, K.nw1);
         const float4 bu = t_lds[sn][K.w - 1][K.lane], bd = t_lds[sn][K.w + 1][K.lane];
         float bl, br;
         if constexpr (WIDE) {
@@ -1461,7 +1574,7 @@ __device__ __forceinline__ void tp_xhalo(const Phi4StepArgs &A, const TbCtx &K, 
         NB[sn] = make_float4(bload1(r1, more ? K.vex : kTpOob, o1), bload1(r1, more ? K.vx2 : kTpOob, o1),
                              bload1(r1, more ? K.vm : kTpOob, o1), bload1(r1, more ? K.vp : kTpOob, o1));
     }
-    const f32x4n n = tb_noise<NZ>(A, R.qz, K.qoff, K.slo, K.shi);
+    const f32x4n n = tb_noise<NZ>(A, noise_prefix(R.qz + K.qoff, K.nw0.a0), K.nw0);
     // lanes 0..7 hold x0-1 (component 3 of its quad), 8..15 x0+256 (component 0)
     const float xi = K.lane >= 8 ? n.a : n.d;
     const float t = tb_site(C[ic], NB[sc].x, NB[sc].y, NB[sc].z, NB[sc].w, C[im], C[ip], xi, A, NZ);
@@ -1500,11 +1613,7 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2p_kernel(const Phi4StepAr
     asm volatile("" : "+v"(K.m2v));
     // periodic: plane k+3 = nz is local plane 0 again; slabs never wrap
     K.swrap_at = A.periodic ? A.nz : INT_MIN;
-    const unsigned long long s0 = ((unsigned long long)A.s_hi << 32) | A.s_lo, s1 = s0 + 1;
-    K.slo = (uint32_t)s0;
-    K.shi = (uint32_t)(s0 >> 32);
-    K.slo1 = (uint32_t)s1;
-    K.shi1 = (uint32_t)(s1 >> 32);
+    tb_noise_words(K, A.nw0, A.nw1);
     const int xl = (x0 == 0 ? Lx : x0) - 1, xr = x0 + 256 == Lx ? 0 : x0 + 256;
     auto wrapy = [Ly](int y) { return y < 0 ? y + Ly : (y >= Ly ? y - Ly : y); };
     const bool xw = WIDE && K.w == kTbWaves;
@@ -1564,6 +1673,7 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2p_kernel(const Phi4StepAr
     // each, the same iteration count), so their registers do not add up
     if (!xw) {
         float4 I[4], T[4], X[2];
+        NoisePre Q[4] = {};  // step s's noise prefixes, by plane index mod 4 as T
         float E[2] = {0.f, 0.f};
         I[0] = bload4(p0, K.voff);
         I[1] = bload4(p1, K.voff);
@@ -1576,15 +1686,18 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2p_kernel(const Phi4StepAr
         T[0] = T[1] = T[2] = T[3] = make_float4(0.f, 0.f, 0.f, 0.f);
         __syncthreads();
         const PrioQ pq(K.z0, z1 - K.z0 + 2);
+        // CY: step s+1 starts from step s's carried noise prefix (tb_plane's),
+        // except in the wide frame instance, which has no VGPRs to spare
+        constexpr bool CY = !(WIDE && FR && WPE == 6);
         for (int k = K.z0 - 1; k <= z1; k += 4) {
-            if (A.prio) prio_by_progress(pq.q(k));
-            tp_row<NZ, WIDE, FR, WH, 0>(A, K, R, k, xrow, vxr, xslot, I, T, X, E, in_lds, t_lds, tx, f1, f2, bmx);
+            if (A.prio) pq.set(k);
+            tp_row<NZ, WIDE, FR, WH, 0, CY>(A, K, R, k, xrow, vxr, xslot, I, T, Q, X, E, in_lds, t_lds, tx, f1, f2, bmx);
             if (k + 1 > z1) break;
-            tp_row<NZ, WIDE, FR, WH, 1>(A, K, R, k + 1, xrow, vxr, xslot, I, T, X, E, in_lds, t_lds, tx, f1, f2, bmx);
+            tp_row<NZ, WIDE, FR, WH, 1, CY>(A, K, R, k + 1, xrow, vxr, xslot, I, T, Q, X, E, in_lds, t_lds, tx, f1, f2, bmx);
             if (k + 2 > z1) break;
-            tp_row<NZ, WIDE, FR, WH, 2>(A, K, R, k + 2, xrow, vxr, xslot, I, T, X, E, in_lds, t_lds, tx, f1, f2, bmx);
+            tp_row<NZ, WIDE, FR, WH, 2, CY>(A, K, R, k + 2, xrow, vxr, xslot, I, T, Q, X, E, in_lds, t_lds, tx, f1, f2, bmx);
             if (k + 3 > z1) break;
-            tp_row<NZ, WIDE, FR, WH, 3>(A, K, R, k + 3, xrow, vxr, xslot, I, T, X, E, in_lds, t_lds, tx, f1, f2, bmx);
+            tp_row<NZ, WIDE, FR, WH, 3, CY>(A, K, R, k + 3, xrow, vxr, xslot, I, T, Q, X, E, in_lds, t_lds, tx, f1, f2, bmx);
         }
     } else {
         float C[4];
@@ -1596,7 +1709,7 @@ __attribute__((amdgpu_waves_per_eu(WPE))) void phi4_tb2p_kernel(const Phi4StepAr
         __syncthreads();
         const PrioQ pq(K.z0, z1 - K.z0 + 2);
         for (int k = K.z0 - 1; k <= z1; k += 4) {
-            if (A.prio) prio_by_progress(pq.q(k));
+            if (A.prio) pq.set(k);
             tp_xhalo<NZ, WH, 0>(A, K, R, k, C, NB, tx);
             if (k + 1 > z1) break;
             tp_xhalo<NZ, WH, 1>(A, K, R, k + 1, C, NB, tx);

@@ -116,11 +116,9 @@ void phi4_tb2_run_kernel(const Phi4StepArgs A0, const Tb2RunArgs R0) {
         if (t > 0) A.fin = 1;  // the previous pair's guarded output
         K.rin = __builtin_amdgcn_make_buffer_rsrc((void *)A.in, (short)0, nbytes, 0x00020000);
         K.rout = __builtin_amdgcn_make_buffer_rsrc((void *)A.out, (short)0, nbytes, 0x00020000);
+        // the kernel advances the step itself: this pair's noise words, once per pair (scalar)
         const unsigned long long s0 = sbase + 2ull * (unsigned long long)t, s1 = s0 + 1;
-        K.slo = (uint32_t)s0;
-        K.shi = (uint32_t)(s0 >> 32);
-        K.slo1 = (uint32_t)s1;
-        K.shi1 = (uint32_t)(s1 >> 32);
+        tb_noise_words(K, phi4_noise_consts(A0.k0, A0.k1, s0), phi4_noise_consts(A0.k0, A0.k1, s1));
         if (t > 0) {
             if (threadIdx.x == 0) {
                 const bool ok = run_wait(R0, lb, A0.nyg, A0.nzc, R0.base + (unsigned int)t);
@@ -151,6 +149,7 @@ void phi4_tb2_run_kernel(const Phi4StepArgs A0, const Tb2RunArgs R0) {
             I1.hp = bload4<LAUX>(r1, K.vp);
         }
         float4 T0 = make_float4(0.f, 0.f, 0.f, 0.f), T1 = T0, T2 = T0;
+        NoisePre Q0{0u, 0u, 0u}, Q1 = Q0, Q2 = Q0;
         FrameAcc f1 = frame_acc(), f2 = frame_acc();  // unused (no records)
         TbRun R;
         R.scur = (uint32_t)tb_pidx(A, K.z0 - 1) * K.pbytes;
@@ -158,16 +157,21 @@ void phi4_tb2_run_kernel(const Phi4StepArgs A0, const Tb2RunArgs R0) {
         R.qz = (uint32_t)global_z(A, K.z0 - 1) * K.qplane;
         R.qzm = 0;
         const int z1 = K.z1;
+        // No carry of the noise prefix here (tb_plane's CY = false): its six
+        // VGPRs take the kernel from 69 to 81, and above 80 a SIMD holds 5 waves,
+        // so two 10-wave blocks (3 + 3 + 2 + 2 waves on the four SIMDs) share a
+        // CU only if the second one's placement mirrors the first's -- and every
+        // block of this grid must be resident.
         for (int p = K.z0 - 1; p <= z1; p += 3) {
-            if (A.prio) prio_by_progress(pq.q(p));
-            tb_plane<NZ, false, false, true, 0, false, LAUX>(A, K, R, p, I0, I1, I2, T0, T1, T2, lds, tx, f1, f2,
-                                                             nullptr);
+            if (A.prio) pq.set(p);
+            tb_plane<NZ, false, false, true, 0, false, LAUX, false, false>(A, K, R, p, I0, I1, I2, T0, T1, T2, Q1, Q2, lds, tx,
+                                                                           f1, f2, nullptr);
             if (p + 1 > z1) break;
-            tb_plane<NZ, false, false, true, 1, false, LAUX>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, lds, tx, f1, f2,
-                                                             nullptr);
+            tb_plane<NZ, false, false, true, 1, false, LAUX, false, false>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, Q2, Q0, lds,
+                                                                           tx, f1, f2, nullptr);
             if (p + 2 > z1) break;
-            tb_plane<NZ, false, false, true, 2, false, LAUX>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, lds, tx, f1, f2,
-                                                             nullptr);
+            tb_plane<NZ, false, false, true, 2, false, LAUX, false, false>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, Q0, Q1, lds,
+                                                                           tx, f1, f2, nullptr);
         }
         // publish pair t: every wave's write-through stores drained, then one flag
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -210,11 +214,7 @@ void phi4_tb2_stage_kernel(const Phi4StepArgs A, const Tb2StageArgs S) {
     K.m2v = f32x2{A.m2, A.m2};
     asm volatile("" : "+v"(K.m2v));
     K.swrap_at = INT_MIN;  // a slab: p < 0 in ghost zones
-    const unsigned long long s0 = ((unsigned long long)A.s_hi << 32) | A.s_lo, s1 = s0 + 1;
-    K.slo = (uint32_t)s0;
-    K.shi = (uint32_t)(s0 >> 32);
-    K.slo1 = (uint32_t)s1;
-    K.shi1 = (uint32_t)(s1 >> 32);
+    tb_noise_words(K, A.nw0, A.nw1);
     {
         auto wrapy = [Ly](int y) { return y < 0 ? y + Ly : (y >= Ly ? y - Ly : y); };
         const int y = wrapy(tbk.yb * kTbRows - 1 + K.w);
@@ -239,6 +239,7 @@ void phi4_tb2_stage_kernel(const Phi4StepArgs A, const Tb2StageArgs S) {
         I1.hp = bload4(r1, K.vp);
     }
     float4 T0 = make_float4(0.f, 0.f, 0.f, 0.f), T1 = T0, T2 = T0;
+    NoisePre Q0{0u, 0u, 0u}, Q1 = Q0, Q2 = Q0;
     FrameAcc f1 = frame_acc(), f2 = frame_acc();  // unused (no records)
     TbRun R;
     R.scur = (uint32_t)tb_pidx(A, K.z0 - 1) * K.pbytes;
@@ -247,16 +248,17 @@ void phi4_tb2_stage_kernel(const Phi4StepArgs A, const Tb2StageArgs S) {
     R.qzm = 0;
     const int z1 = K.z1;
     const PrioQ pq(K.z0, z1 - K.z0 + 2);
-    for (int p = K.z0 - 1; p <= z1; p += 3) {
-        if (A.prio) prio_by_progress(pq.q(p));
-        tb_plane<NZ, false, false, true, 0, false, 0, true>(A, K, R, p, I0, I1, I2, T0, T1, T2, lds, tx, f1, f2,
+    for (int p = K.z0 - 1; p <= z1; p += 3) {  // one exit, as phi4_tb2_kernel's march
+        if (A.prio) pq.set(p);
+        tb_plane<NZ, false, false, true, 0, false, 0, true>(A, K, R, p, I0, I1, I2, T0, T1, T2, Q1, Q2, lds, tx, f1, f2,
                                                             nullptr);
-        if (p + 1 > z1) break;
-        tb_plane<NZ, false, false, true, 1, false, 0, true>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, lds, tx, f1, f2,
-                                                            nullptr);
-        if (p + 2 > z1) break;
-        tb_plane<NZ, false, false, true, 2, false, 0, true>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, lds, tx, f1, f2,
-                                                            nullptr);
+        if (p + 1 <= z1) {
+            tb_plane<NZ, false, false, true, 1, false, 0, true>(A, K, R, p + 1, I1, I2, I0, T1, T2, T0, Q2, Q0, lds, tx, f1, f2,
+                                                                nullptr);
+            if (p + 2 <= z1)
+                tb_plane<NZ, false, false, true, 2, false, 0, true>(A, K, R, p + 2, I2, I0, I1, T2, T0, T1, Q0, Q1, lds, tx, f1,
+                                                                    f2, nullptr);
+        }
     }
     // every wave's write-through stores drained, then one count for the block
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

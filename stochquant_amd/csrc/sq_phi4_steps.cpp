@@ -37,6 +37,8 @@ sq::Phi4StepArgs phi4_base_args(sq_ctx *c, const Slab &s, int in_buf) {
     a.k1 = (uint32_t)(c->p.seed >> 32);
     a.s_lo = (uint32_t)c->step;
     a.s_hi = (uint32_t)(c->step >> 32);
+    a.nw0 = sq::phi4_noise_consts(a.k0, a.k1, c->step);
+    a.nw1 = sq::phi4_noise_consts(a.k0, a.k1, c->step + 1);
     a.flag = c->in_frame ? c->flag : nullptr;  // the guard flag only feeds a frame's rollback
     a.st_md = nullptr;
     a.st_a = nullptr;

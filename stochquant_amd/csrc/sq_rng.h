@@ -17,17 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sq_noise_consts.h"  // the Philox constants and the noise streams
+
 namespace sq {
-
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
-constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u;
-constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
-
-// Noise streams (bits 24..31 of counter word 1).
-constexpr uint32_t kStreamField = 0;  // per-site field noise
-constexpr uint32_t kStreamOmega = 1;  // QM1D collective coordinate
-constexpr uint32_t kStreamInit = 2;   // initial field
 
 struct u32x4 {
     uint32_t x, y, z, w;
