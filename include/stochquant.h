@@ -427,6 +427,61 @@ int sq_phi4_ens_moments(sq_phi4_ens *e, int first, int count, double *out5);
 int sq_phi4_ens_flags(sq_phi4_ens *e, int first, int count, int *flags, int clear);
 int sq_phi4_ens_perf(sq_phi4_ens *e, sq_perf_t *out);
 
+/* The ensemble's zero-momentum time-slice correlator over z, accumulated over
+ * Langevin time inside the resident kernels.  For one replica of shape (Lx,
+ * Ly, Lz): V = Lx Ly Lz, nt = Lz / 2 + 1 (integer division).
+ *
+ * Slice sums: S(z) = sum_{x,y} phi(x, y, z), in double from the fp32 field, in
+ * a fixed order that depends on the lattice shape only: the slice's float4
+ * quads (x fastest, then y) q = 0 .. Lx Ly / 4 - 1 are dealt to 64 lanes, lane
+ * l adds its quads l, l + 64, ... in ascending order to 0.0, each quad as
+ * (x + y) + (z + w), and the 64 lane sums are combined by the inclusive-scan
+ * sequence of distances 1, 2, 4, 8 within rows of 16 lanes, then row 0 + row 1
+ * and row 2 + row 3 onto rows 1 and 3, then row 1's total onto rows 2 and 3;
+ * lane 63 holds S(z).  No floating-point atomics.  The bits of S do not depend
+ * on nrep, the replica's index, the work-group shape, whether the measurement
+ * ran in flight or stand-alone, or how calls were split.
+ *
+ * One measurement: g(t) = sum_{z=0}^{Lz-1} S(z) S((z + t) mod Lz) for t = 0 ..
+ * nt - 1, z ascending from 0.0, every product and every sum rounded once to
+ * double (no fused multiply-add); not divided by V.  g(Lz - t) = g(t), so nt
+ * values are kept.  s1 = sum_z S(z), z ascending from 0.0.
+ *
+ * Accumulators, per replica, in device memory, persistent across calls, zero
+ * at creation and cleared by sq_phi4_ens_corr_reset only (uploads, set_params,
+ * set_step and set_stability leave them alone): G[nt] doubles, S1 one double,
+ * nmeas one 64-bit integer.  A measurement does G[t] = G[t] + g(t), S1 = S1 +
+ * s1, nmeas += 1, one addition each, so calls split in any way add up to the
+ * same bits.
+ *
+ * sq_phi4_ens_step_corr: as sq_phi4_ens_step(e, nsteps, every, series) for
+ * fields, counters, flags and series (series nullable); additionally one
+ * measurement after each every-th step of the call (every >= 1, else
+ * SQ_E_ARG; an incomplete tail measures nothing, as for series).
+ * sq_phi4_ens_run_frames_corr: as sq_phi4_ens_run_frames for verdicts, dtau,
+ * fields, T, V, records and series; additionally one measurement of the
+ * adopted field after every STABLE frame of a replica; a rolled-back frame
+ * measures nothing.  sq_phi4_ens_corr_sums: the raw accumulators of replicas
+ * [first, first + count): G count rows of nt, S1 and nmeas count entries; any
+ * may be NULL.  sq_phi4_ens_slices: one measurement of the CURRENT fields,
+ * accumulating nothing: S count rows of Lz, g count rows of nt; either may be
+ * NULL.  sq_phi4_ens_correlator: replica statistics, on the host in double,
+ * replicas in index order, only those with nmeas > 0 (*used = how many; none:
+ * SQ_E_STATE): c_r(t) = G_r(t) / (nmeas_r V), minus (S1_r / nmeas_r)^2 / (Lz V)
+ * when connected != 0 (tauhost's cbar - Lz sbar^2 / V); mean[t] over those
+ * replicas and err[t] = sqrt(sum_r (c_r - mean)^2 / (u (u - 1))), 0 for u = 1;
+ * n <= nt; err and used may be NULL.  sq_phi4_ens_corr_shape_info (no device,
+ * no handle; SQ_E_ARG as sq_phi4_ens_shape_info): out = {LDS images and dynamic
+ * LDS bytes of the step launch with the correlator, the same two of the
+ * frames launch with it, LDS bytes of the slices launch, nt}. */
+int sq_phi4_ens_step_corr(sq_phi4_ens *e, int nsteps, int every, double *series);
+int sq_phi4_ens_run_frames_corr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series);
+int sq_phi4_ens_corr_sums(sq_phi4_ens *e, int first, int count, double *G, double *S1, long long *nmeas);
+int sq_phi4_ens_corr_reset(sq_phi4_ens *e, int first, int count);
+int sq_phi4_ens_slices(sq_phi4_ens *e, int first, int count, double *S, double *g);
+int sq_phi4_ens_correlator(sq_phi4_ens *e, int connected, double *mean, double *err, int n, int *used);
+int sq_phi4_ens_corr_shape_info(const int dims[3], int out[6]);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

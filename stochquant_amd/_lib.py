@@ -189,6 +189,14 @@ SIGNATURES = {
     "sq_phi4_ens_moments": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
     "sq_phi4_ens_flags": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int]),
     "sq_phi4_ens_perf": (ctypes.c_int, [_P, ctypes.POINTER(SqPerf)]),
+    "sq_phi4_ens_step_corr": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_phi4_ens_run_frames_corr": (ctypes.c_int, [_P, ctypes.c_int, _I, _D, _D]),
+    "sq_phi4_ens_corr_sums": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D,
+                                             ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ens_corr_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_slices": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D]),
+    "sq_phi4_ens_correlator": (ctypes.c_int, [_P, ctypes.c_int, _D, _D, ctypes.c_int, _I]),
+    "sq_phi4_ens_corr_shape_info": (ctypes.c_int, [_I, _I]),
 }
 
 _lib = None

@@ -37,6 +37,12 @@ struct sq_phi4_ens {
     double *fr_dtau = nullptr;           // ... and Δτ
     size_t fr_cap = 0;                   // ... in frames
     unsigned long long adv = 0;          // steps run since the records were written
+    int nt = 0;                          // Lz / 2 + 1 correlator distances
+    double *cG = nullptr;                // [R][nt] correlator accumulators: zero at creation, cleared by
+    double *cS1 = nullptr;               // [R]     sq_phi4_ens_corr_reset only
+    long long *cN = nullptr;             // [R]
+    double *ctmp = nullptr;              // sq_phi4_ens_slices' device buffer: [count][Lz] then [count][nt]
+    size_t ctmp_cap = 0;                 // ... in replicas
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -123,6 +129,13 @@ void release_phi4_ens(sq_phi4_ens *e) {
     (void)hipFree(e->frecs);
     (void)hipFree(e->fr_stable);
     (void)hipFree(e->fr_dtau);
+    (void)hipFree(e->cG);
+    (void)hipFree(e->cS1);
+    (void)hipFree(e->cN);
+    (void)hipFree(e->ctmp);
+    e->cG = e->cS1 = e->ctmp = nullptr;
+    e->cN = nullptr;
+    e->ctmp_cap = 0;
     e->fst_dev = nullptr;
     e->frecs = nullptr;
     e->fr_stable = nullptr;
@@ -133,6 +146,47 @@ void release_phi4_ens(sq_phi4_ens *e) {
     e->flags = nullptr;
     e->series = e->mom = nullptr;
     e->series_cap = 0;
+}
+
+sq::Phi4EnsCorrArgs ens_corr_args(const sq_phi4_ens *e) {
+    sq::Phi4EnsCorrArgs c{};
+    c.G = e->cG;
+    c.S1 = e->cS1;
+    c.nmeas = e->cN;
+    return c;
+}
+
+// sq_phi4_ens_step (corr = false) and sq_phi4_ens_step_corr (corr = true; every >= 1 checked by the caller)
+int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr) {
+    if (nsteps == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    int rc = ens_sync_recs(e);
+    if (rc) return rc;
+    const size_t nrec = (every > 0 && series) ? (size_t)(nsteps / every) : 0;
+    const size_t nd = nrec * (size_t)e->R * 4;
+    if (nd > e->series_cap) {
+        // the records go straight to pinned host memory (32 B per replica and record, posted writes), visible
+        // once the stream is idle: a device buffer and its copy back cost a fixed 15-20 us per call (a 200-step
+        // call of one 8^3 lattice with every = 20: 24 % over every = 0 with the copy, 13 % without)
+        (void)hipHostFree(e->series);
+        e->series = nullptr;
+        e->series_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
+        e->series_cap = nd;
+    }
+    sq::Phi4EnsArgs a = ens_args(e);
+    a.nsteps = nsteps;
+    a.every = (nd || corr) ? every : 0;
+    a.series = nd ? e->series : nullptr;
+    if (corr) SQ_HIP(sq::phi4_ens_step_corr_launch(a, ens_corr_args(e), e->R, e->stream));
+    else SQ_HIP(sq::phi4_ens_step_launch(a, e->R, e->stream));
+    e->launches++;
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    e->adv += (unsigned long long)nsteps;
+    for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
+    e->steps_total += (long long)nsteps * e->R;
+    return SQ_OK;
 }
 
 }  // namespace
@@ -176,6 +230,13 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         SQ_HIP(hipMalloc(&e->flags, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->mom, sizeof(double) * 5 * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->fst_dev, sizeof(sq::Phi4EnsFrameState) * (size_t)nrep));
+        e->nt = e->Lz / 2 + 1;
+        SQ_HIP(hipMalloc(&e->cG, sizeof(double) * (size_t)e->nt * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->cS1, sizeof(double) * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->cN, sizeof(long long) * (size_t)nrep));
+        SQ_HIP(hipMemset(e->cG, 0, sizeof(double) * (size_t)e->nt * (size_t)nrep));
+        SQ_HIP(hipMemset(e->cS1, 0, sizeof(double) * (size_t)nrep));
+        SQ_HIP(hipMemset(e->cN, 0, sizeof(long long) * (size_t)nrep));
         SQ_HIP(hipMemset(e->field, 0, bytes));
         SQ_HIP(hipMemset(e->flags, 0, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -302,37 +363,33 @@ int sq_phi4_ens_step(sq_phi4_ens *e, int nsteps, int every, double *series) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
     if (every < 0) return fail(SQ_E_ARG, "every must be >= 0");
-    if (nsteps == 0) return SQ_OK;
-    DeviceGuard g(e->dev);
-    int rc = ens_sync_recs(e);
-    if (rc) return rc;
-    const size_t nrec = (every > 0 && series) ? (size_t)(nsteps / every) : 0;
-    const size_t nd = nrec * (size_t)e->R * 4;
-    if (nd > e->series_cap) {
-        // the records go straight to pinned host memory (32 B per replica and record, posted writes), visible
-        // once the stream is idle: a device buffer and its copy back cost a fixed 15-20 us per call (a 200-step
-        // call of one 8^3 lattice with every = 20: 24 % over every = 0 with the copy, 13 % without)
-        (void)hipHostFree(e->series);
-        e->series = nullptr;
-        e->series_cap = 0;
-        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
-        e->series_cap = nd;
-    }
-    sq::Phi4EnsArgs a = ens_args(e);
-    a.nsteps = nsteps;
-    a.every = nd ? every : 0;
-    a.series = nd ? e->series : nullptr;
-    SQ_HIP(sq::phi4_ens_step_launch(a, e->R, e->stream));
-    e->launches++;
-    SQ_HIP(hipStreamSynchronize(e->stream));
-    if (nd) memcpy(series, e->series, sizeof(double) * nd);
-    e->adv += (unsigned long long)nsteps;
-    for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
-    e->steps_total += (long long)nsteps * e->R;
-    return SQ_OK;
+    return ens_step(e, nsteps, every, series, false);
+}
+
+int sq_phi4_ens_step_corr(sq_phi4_ens *e, int nsteps, int every, double *series) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (every < 1) return fail(SQ_E_ARG, "a correlator measurement needs every >= 1");
+    return ens_step(e, nsteps, every, series, true);
+}
+
+namespace {
+int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr);
 }
 
 int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
+    return ens_run_frames(e, nframes, stable, dtau, series, false);
+}
+
+int sq_phi4_ens_run_frames_corr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
+    return ens_run_frames(e, nframes, stable, dtau, series, true);
+}
+
+}  // extern "C"
+
+namespace {
+
+int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
     if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
@@ -382,7 +439,8 @@ int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dta
     f.nframes = nframes;
     f.loops = L;
     f.adapt = e->p.adapt_dtau ? 1 : 0;
-    SQ_HIP(sq::phi4_ens_frames_launch(a, f, e->R, e->stream));
+    if (corr) SQ_HIP(sq::phi4_ens_frames_corr_launch(a, f, ens_corr_args(e), e->R, e->stream));
+    else SQ_HIP(sq::phi4_ens_frames_launch(a, f, e->R, e->stream));
     e->launches++;
     SQ_HIP(hipMemcpyAsync(e->fst.data(), e->fst_dev, sizeof(sq::Phi4EnsFrameState) * R, hipMemcpyDeviceToHost,
                           e->stream));
@@ -396,6 +454,109 @@ int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dta
         e->steps_total += e->fst[r].exec;
     }
     e->rec_dirty = true;  // Δτ and the counters moved
+    return SQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_corr_sums(sq_phi4_ens *e, int first, int count, double *G, double *S1, long long *nmeas) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t nt = (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    if (G) SQ_HIP(hipMemcpy(G, e->cG + f * nt, sizeof(double) * n * nt, hipMemcpyDeviceToHost));
+    if (S1) SQ_HIP(hipMemcpy(S1, e->cS1 + f, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (nmeas) SQ_HIP(hipMemcpy(nmeas, e->cN + f, sizeof(long long) * n, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_corr_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t nt = (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    SQ_HIP(hipMemsetAsync(e->cG + f * nt, 0, sizeof(double) * n * nt, e->stream));
+    SQ_HIP(hipMemsetAsync(e->cS1 + f, 0, sizeof(double) * n, e->stream));
+    SQ_HIP(hipMemsetAsync(e->cN + f, 0, sizeof(long long) * n, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_slices(sq_phi4_ens *e, int first, int count, double *S, double *g) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0 || (!S && !g)) return SQ_OK;
+    DeviceGuard dg(e->dev);
+    const size_t nt = (size_t)e->nt, Lz = (size_t)e->Lz, n = (size_t)count;
+    if (n > e->ctmp_cap) {
+        (void)hipFree(e->ctmp);
+        e->ctmp = nullptr;
+        e->ctmp_cap = 0;
+        SQ_HIP(hipMalloc(&e->ctmp, sizeof(double) * n * (Lz + nt)));
+        e->ctmp_cap = n;
+    }
+    double *devS = e->ctmp, *devg = e->ctmp + n * Lz;
+    SQ_HIP(sq::phi4_ens_slices_launch(ens_args(e), first, count, devS, devg, e->stream));
+    if (S) SQ_HIP(hipMemcpyAsync(S, devS, sizeof(double) * n * Lz, hipMemcpyDeviceToHost, e->stream));
+    if (g) SQ_HIP(hipMemcpyAsync(g, devg, sizeof(double) * n * nt, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_correlator(sq_phi4_ens *e, int connected, double *mean, double *err, int n, int *used) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (n < 0 || n > e->nt) return fail(SQ_E_ARG, "n must lie in [0, Lz / 2 + 1]");
+    if (!mean && n > 0) return fail(SQ_E_ARG, "null argument");
+    const size_t R = (size_t)e->R, nt = (size_t)e->nt;
+    std::vector<double> G(R * nt), S1(R);
+    std::vector<long long> N(R);
+    int rc = sq_phi4_ens_corr_sums(e, 0, e->R, G.data(), S1.data(), N.data());
+    if (rc) return rc;
+    int u = 0;
+    for (size_t r = 0; r < R; ++r) u += N[r] > 0 ? 1 : 0;
+    if (used) *used = u;
+    if (u == 0) return fail(SQ_E_STATE, "no replica has a correlator measurement");
+    const double V = (double)e->sites, Lz = (double)e->Lz;
+    std::vector<double> c((size_t)u);
+    for (int t = 0; t < n; ++t) {
+        size_t k = 0;
+        double sum = 0.0;
+        for (size_t r = 0; r < R; ++r) {
+            if (N[r] <= 0) continue;
+            const double nm = (double)N[r];
+            double v = G[r * nt + (size_t)t] / (nm * V);
+            if (connected) {
+                const double sb = S1[r] / nm;
+                v -= sb * sb / (Lz * V);
+            }
+            c[k++] = v;
+            sum += v;
+        }
+        const double m = sum / (double)u;
+        mean[t] = m;
+        if (err) {
+            double q = 0.0;
+            for (int i = 0; i < u; ++i) q += (c[(size_t)i] - m) * (c[(size_t)i] - m);
+            err[t] = u > 1 ? sqrt(q / ((double)u * (double)(u - 1))) : 0.0;
+        }
+    }
+    return SQ_OK;
+}
+
+int sq_phi4_ens_corr_shape_info(const int dims[3], int out[6]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
+    out[0] = s.co_two ? 2 : 1;
+    out[1] = s.co_lds_bytes;
+    out[2] = s.co_fr_two ? 2 : 1;
+    out[3] = s.co_fr_lds_bytes;
+    out[4] = s.sl_lds_bytes;
+    out[5] = dims[2] / 2 + 1;
     return SQ_OK;
 }
 

@@ -64,6 +64,14 @@ struct Phi4EnsFrameArgs {
     int nframes, loops, adapt;
 };
 
+// One replica's correlator accumulators: G(t) += g(t), S1 += sum_z S(z), nmeas += 1 per
+// measurement, nt = Lz / 2 + 1.  An argument of its own: Phi4EnsArgs is the plain instances' and stays.
+struct Phi4EnsCorrArgs {
+    double *G;          // [R][nt]
+    double *S1;         // [R]
+    long long *nmeas;   // [R]
+};
+
 // Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
 // quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and per
 // launch whether two LDS images fit (one barrier per step instead of two) and
@@ -76,14 +84,29 @@ struct Phi4EnsShape {
     bool fr_two;        // the frames launch (kPhi4EnsFrameScratchBytes behind the images)
     int fr_lds_bytes;
     int mom_lds_bytes;  // the moments launch: always one image
+    // the correlator launches (Lz > 0): the same layouts with Lz doubles, the slice sums, behind the
+    // launch's scratch; a shape with two images in the plain launch may have one here
+    bool co_two;        // the step launch with the correlator
+    int co_lds_bytes;
+    bool co_fr_two;     // the frames launch with the correlator
+    int co_fr_lds_bytes;
+    int sl_lds_bytes;   // the slices launch: one image, the scratch, the slice sums
 };
-Phi4EnsShape phi4_ens_shape(int sites);
+Phi4EnsShape phi4_ens_shape(int sites, int Lz = 0);
 
 // nsteps steps of every replica in one launch (grid = nrep work-groups).
 hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s);
 // nframes frames of every replica in one launch (grid = nrep work-groups); a.series nullable:
 // [nframes][R][4] sums of the field after each frame's verdict.  a.nsteps / a.every are not used.
 hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, int nrep, hipStream_t s);
+// The two above with one correlator measurement (ens_corr) after each every-th step (a.every >= 1; a.series
+// nullable) / after every stable frame of a replica, accumulated in place into c's rows.
+hipError_t phi4_ens_step_corr_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs &c, int nrep, hipStream_t s);
+hipError_t phi4_ens_frames_corr_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs &c,
+                                       int nrep, hipStream_t s);
+// One measurement of the stored fields of replicas first .. first + count, accumulating nothing:
+// S[r][Lz] slice sums, g[r][nt] (device memory, both non-null).
+hipError_t phi4_ens_slices_launch(const Phi4EnsArgs &a, int first, int count, double *S, double *g, hipStream_t s);
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

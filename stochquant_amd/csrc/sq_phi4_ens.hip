@@ -32,6 +32,11 @@
 // step the block's stability record behind the step's own barrier, the rule,
 // an early exit once it has fired; per frame the verdict, the Δτ controller
 // and the store to / reload from the replica's HBM field, its snapshot.
+//
+// The correlator instances of both kernels add ens_corr, the zero-momentum
+// time-slice correlator over z of the field in the image, accumulated per
+// replica in device memory; phi4_ens_slices_kernel is the same routine on the
+// stored field.
 #define SQ_PHI4_KERNELS_ONLY
 #include "sq_phi4.hip"
 #include "sq_phi4_ens.h"
@@ -188,6 +193,58 @@ __device__ __forceinline__ void ens_fold(double (&s)[4], float mx, double *scr, 
     }
 }
 
+// One time-slice correlator measurement of the field in img.
+// Slice sums: wave w takes slices w, w + nw, ...; its lanes stride the slice's
+// quads in ascending order, each quad (x + y) + (z + w) in double, the wave by
+// ens_wave_sum, S(z) to Sl[z]: the bits depend on the slice's shape and sites
+// only.  One barrier, then lane t (and t + T) forms g(t) = sum_z S(z) S((z + t)
+// mod Lz), z ascending, every product and sum rounded once, and lane T - 1
+// s1 = sum_z S(z).  ACC: G[t] = G[t] + g(t), S1 += s1, nmeas += 1 in place (the
+// same lane owns an entry for the whole call); else G[t] = g(t) and, Sout
+// given, the slice sums to it.  Every lane of the block calls it; Sl is free
+// again after the next block barrier.
+template <bool ACC>
+__device__ __forceinline__ void ens_corr(const EnsGeo &g, int Lz, const float *img, double *Sl, double *G, double *S1,
+                                         long long *nm, double *Sout) {
+#pragma clang fp contract(off)
+    const float4 *img4 = reinterpret_cast<const float4 *>(img);
+    const int T = blockDim.x, lane = threadIdx.x & 63, nw = T >> 6;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    for (int z = w; z < Lz; z += nw) {  // wave-uniform: every lane reaches the scan
+        const float4 *sl = img4 + z * g.qplane;
+        double a = 0.0;
+        for (int i = lane; i < g.qplane; i += 64) {
+            const float4 v = sl[i];
+            a += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+        }
+        a = ens_wave_sum(a);
+        if (lane == 63) Sl[z] = a;
+    }
+    __syncthreads();
+    const int nt = Lz / 2 + 1;
+    for (int t = threadIdx.x; t < nt; t += T) {
+        double old = 0.0;
+        if (ACC) old = G[t];
+        double acc = 0.0;
+        int zt = t;
+        for (int z = 0; z < Lz; ++z) {
+            acc = __dadd_rn(acc, __dmul_rn(Sl[z], Sl[zt]));
+            zt = zt + 1 == Lz ? 0 : zt + 1;
+        }
+        G[t] = ACC ? __dadd_rn(old, acc) : acc;
+    }
+    if (ACC) {
+        if ((int)threadIdx.x == T - 1) {
+            double s = 0.0;
+            for (int z = 0; z < Lz; ++z) s = __dadd_rn(s, Sl[z]);
+            *S1 = __dadd_rn(*S1, s);
+            *nm += 1;
+        }
+    } else if (Sout != nullptr) {
+        for (int z = threadIdx.x; z < Lz; z += T) Sout[z] = Sl[z];
+    }
+}
+
 template <int K>
 __device__ __forceinline__ void ens_load(const Phi4EnsArgs &E, const EnsGeo &g, int r, float4 (&c)[K],
                                          uint32_t (&fl)[K], float *img) {
@@ -207,9 +264,25 @@ __device__ __forceinline__ void ens_load(const Phi4EnsArgs &E, const EnsGeo &g, 
     __syncthreads();
 }
 
+// The correlator instances of the step and frames kernels are the same kernel
+// templates with one trailing Phi4EnsCorrArgs argument (CA = {Phi4EnsCorrArgs});
+// the plain instances (CA empty) keep their argument list and, every
+// correlator statement being behind `if constexpr`, their code.
+template <typename... CA>
+__device__ __forceinline__ Phi4EnsCorrArgs ens_corr_args(const CA &...c) {
+    static_assert(sizeof...(CA) <= 1, "at most one Phi4EnsCorrArgs");
+    const Phi4EnsCorrArgs a[] = {c..., Phi4EnsCorrArgs{}};
+    return a[0];
+}
+
 // two != 0: two LDS images (the launcher sized the dynamic LDS for them).
-template <int K>
-__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const Phi4EnsArgs E, const int two) {
+// With the correlator: one ens_corr measurement after each every-th step into
+// the replica's rows, the slice sums behind the scratch; the series as without
+// it when E.series is given.
+template <int K, typename... CA>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const Phi4EnsArgs E, const int two,
+                                                                          const CA... ca) {
+    constexpr bool CORR = sizeof...(CA) != 0;
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
@@ -251,13 +324,20 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const P
         for (int j = 0; j < K; ++j)
             if (fl[j] & kEnsValid) cur4[(int)threadIdx.x + j * T] = c[j];
         __syncthreads();
-        if (E.series != nullptr && --left == 0) {
+        if ((CORR || E.series != nullptr) && --left == 0) {
             left = E.every;
-            double sm[4];
-            float mx;
-            ens_sums<K>(g, c, fl, cur, sm, mx);
-            ens_fold(sm, mx, scr, E.series + 4 * ((size_t)rec * gridDim.x + (size_t)r), false);
-            ++rec;
+            if (!CORR || E.series != nullptr) {
+                double sm[4];
+                float mx;
+                ens_sums<K>(g, c, fl, cur, sm, mx);
+                ens_fold(sm, mx, scr, E.series + 4 * ((size_t)rec * gridDim.x + (size_t)r), false);
+                ++rec;
+            }
+            if constexpr (CORR) {
+                const Phi4EnsCorrArgs C = ens_corr_args(ca...);
+                ens_corr<true>(g, E.Lz, cur, scr + kPhi4EnsScratchBytes / 8, C.G + (size_t)r * (size_t)(E.Lz / 2 + 1),
+                               C.S1 + r, C.nmeas + r, nullptr);
+            }
         }
     }
     float4 *gf = reinterpret_cast<float4 *>(E.field + (size_t)r * (size_t)(4 * g.Q));
@@ -335,9 +415,15 @@ __device__ __forceinline__ void ens_step_fr(const Phi4StepArgs &A, const EnsGeo 
 // The step records rotate through three LDS slots: step s posts to slot s % 3
 // before its barrier, every lane reads it after, and lane 0 then clears slot
 // (s + 2) % 3 -- last read before this barrier, next posted after the next one.
-template <int K>
+//
+// CORR: one ens_corr measurement of the adopted field after every stable frame
+// (after the verdict: cur holds that field and every wave is past the last
+// step's barrier); a rolled-back frame measures nothing.
+template <int K, typename... CA>
 __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const Phi4EnsArgs E,
-                                                                            const Phi4EnsFrameArgs F, const int two) {
+                                                                            const Phi4EnsFrameArgs F, const int two,
+                                                                            const CA... ca) {
+    constexpr bool CORR = sizeof...(CA) != 0;
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
@@ -498,6 +584,13 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const
             ens_sums<K>(g, c, fl, cur, sm, mx);
             ens_fold(sm, mx, scr, E.series + 4 * ((size_t)f * gridDim.x + (size_t)r), false);
         }
+        if constexpr (CORR) {
+            if (stable) {  // block-uniform: every lane decided the frame from the same records
+                const Phi4EnsCorrArgs C = ens_corr_args(ca...);
+                ens_corr<true>(g, E.Lz, cur, reinterpret_cast<double *>(sb + kPhi4EnsFrameScratchBytes),
+                               C.G + (size_t)r * (size_t)(E.Lz / 2 + 1), C.S1 + r, C.nmeas + r, nullptr);
+            }
+        }
     }
     if (threadIdx.x == 0) {
         Phi4EnsFrameState o = st;
@@ -530,6 +623,22 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_moments_kernel(cons
     ens_fold(sm, mx, scr, out + 5 * (size_t)blockIdx.x, true);
 }
 
+// ens_corr on the stored field of replica first + blockIdx.x, accumulating
+// nothing: S[blockIdx.x][Lz], g[blockIdx.x][nt].
+template <int K>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_slices_kernel(const Phi4EnsArgs E, const int first,
+                                                                            double *S, double *gout) {
+    const int r = first + blockIdx.x;
+    const EnsGeo g = ens_geo(E);
+    float *img = reinterpret_cast<float *>(ens_smem);
+    double *Sl = reinterpret_cast<double *>(ens_smem + 16 * (size_t)g.Q + kPhi4EnsScratchBytes);
+    float4 c[K];
+    uint32_t fl[K];
+    ens_load<K>(E, g, r, c, fl, img);  // ends in a barrier
+    ens_corr<false>(g, E.Lz, img, Sl, gout + (size_t)blockIdx.x * (size_t)(E.Lz / 2 + 1), nullptr, nullptr,
+                    S + (size_t)blockIdx.x * (size_t)E.Lz);
+}
+
 // phi4_init_kernel's field for every replica (blockIdx.y) from its own key.
 __global__ __launch_bounds__(256) void phi4_ens_init_kernel(const Phi4EnsArgs E, const float amp) {
     const int r = blockIdx.y;
@@ -557,7 +666,7 @@ bool ens_shape_ok(const Phi4EnsArgs &a) {
 
 }  // namespace
 
-Phi4EnsShape phi4_ens_shape(int sites) {
+Phi4EnsShape phi4_ens_shape(int sites, int Lz) {
     Phi4EnsShape s;
     const int Q = sites / 4;
     s.K = Q <= kPhi4EnsMaxLanes ? 1 : (Q <= 2 * kPhi4EnsMaxLanes ? 2 : (Q <= 4 * kPhi4EnsMaxLanes ? 4 : 8));
@@ -568,6 +677,13 @@ Phi4EnsShape phi4_ens_shape(int sites) {
     s.fr_two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes <= kPhi4EnsLdsBytes;
     s.fr_lds_bytes = (s.fr_two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes;
     s.mom_lds_bytes = 4 * sites + kPhi4EnsScratchBytes;
+    // the correlator launches: Lz doubles behind the scratch, sized by their own rule
+    const int sl = 8 * Lz;
+    s.co_two = 2 * 4 * sites + kPhi4EnsScratchBytes + sl <= kPhi4EnsLdsBytes;
+    s.co_lds_bytes = (s.co_two ? 2 : 1) * 4 * sites + kPhi4EnsScratchBytes + sl;
+    s.co_fr_two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes + sl <= kPhi4EnsLdsBytes;
+    s.co_fr_lds_bytes = (s.co_fr_two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes + sl;
+    s.sl_lds_bytes = 4 * sites + kPhi4EnsScratchBytes + sl;
     return s;
 }
 
@@ -588,6 +704,24 @@ hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s) {
     return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.lds_bytes, s);
 }
 
+hipError_t phi4_ens_step_corr_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs &c, int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < 1 || c.G == nullptr ||
+        c.S1 == nullptr || c.nmeas == nullptr)
+        return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    Phi4EnsArgs q = a;
+    Phi4EnsCorrArgs cq = c;
+    int two = sh.co_two ? 1 : 0;
+    void *args[] = {&q, &two, &cq};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_step_kernel<1, Phi4EnsCorrArgs>
+                     : sh.K == 2 ? (const void *)&phi4_ens_step_kernel<2, Phi4EnsCorrArgs>
+                     : sh.K == 4 ? (const void *)&phi4_ens_step_kernel<4, Phi4EnsCorrArgs>
+                                 : (const void *)&phi4_ens_step_kernel<8, Phi4EnsCorrArgs>;
+    hipError_t e = ens_lds_attr(fn, sh.co_lds_bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.co_lds_bytes, s);
+}
+
 hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, int nrep, hipStream_t s) {
     if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
         f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr)
@@ -605,6 +739,43 @@ hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &
     hipError_t e = ens_lds_attr(fn, bytes);
     if (e != hipSuccess) return e;
     return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+}
+
+hipError_t phi4_ens_frames_corr_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs &c,
+                                       int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
+        f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr || c.G == nullptr || c.S1 == nullptr ||
+        c.nmeas == nullptr)
+        return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    int two = sh.co_fr_two ? 1 : 0;
+    const int bytes = sh.co_fr_lds_bytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsFrameArgs fq = f;
+    Phi4EnsCorrArgs cq = c;
+    void *args[] = {&q, &fq, &two, &cq};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_frames_kernel<1, Phi4EnsCorrArgs>
+                     : sh.K == 2 ? (const void *)&phi4_ens_frames_kernel<2, Phi4EnsCorrArgs>
+                     : sh.K == 4 ? (const void *)&phi4_ens_frames_kernel<4, Phi4EnsCorrArgs>
+                                 : (const void *)&phi4_ens_frames_kernel<8, Phi4EnsCorrArgs>;
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+}
+
+hipError_t phi4_ens_slices_launch(const Phi4EnsArgs &a, int first, int count, double *S, double *g, hipStream_t s) {
+    if (!ens_shape_ok(a) || first < 0 || count < 1 || S == nullptr || g == nullptr) return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    const int bytes = sh.sl_lds_bytes;
+    Phi4EnsArgs q = a;
+    void *args[] = {&q, &first, &S, &g};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_slices_kernel<1>
+                     : sh.K == 2 ? (const void *)&phi4_ens_slices_kernel<2>
+                     : sh.K == 4 ? (const void *)&phi4_ens_slices_kernel<4>
+                                 : (const void *)&phi4_ens_slices_kernel<8>;
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)count), dim3((unsigned)sh.T), args, (size_t)bytes, s);
 }
 
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s) {

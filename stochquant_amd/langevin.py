@@ -660,29 +660,40 @@ class Phi4Ensemble:
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64), (self.R,)))
         _lib.call("sq_phi4_ens_set_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
 
-    def step(self, n=1, every=0):
+    def step(self, n=1, every=0, correlate=False):
         """n steps of every replica in one launch.  every = k > 0: returns the
         (n // k, R, 4) array of S1 = Σφ, S2 = Σφ², S4 = Σφ⁴ and NN = Σ over
         sites and the three forward links of φ(x) φ(x + μ), recorded after each
-        k-th step from the on-chip field; otherwise None."""
+        k-th step from the on-chip field; otherwise None.  `correlate` (needs
+        every >= 1): the kernel also adds one time-slice correlator measurement
+        after each k-th step to the replicas' accumulators (`corr_sums`,
+        `correlator`); fields, counters, flags and the return value are those of
+        the same call without it."""
         n, every = int(n), int(every)
+        fn = "sq_phi4_ens_step"
+        if correlate:
+            if every < 1:
+                raise ValueError("correlate=True needs every >= 1")
+            fn = "sq_phi4_ens_step_corr"
         if every <= 0:
-            _lib.call("sq_phi4_ens_step", self._h, n, 0, None)
+            _lib.call(fn, self._h, n, 0, None)
             return None
         ser = np.zeros((max(n, 0) // every, self.R, 4))
-        _lib.call("sq_phi4_ens_step", self._h, n, every, _dptr(ser) if ser.size else None)
+        _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None)
         return ser
 
-    def run_frames(self, n, measure=False):
+    def run_frames(self, n, measure=False, correlate=False):
         """n frames of every replica in one launch: (stable (n, R) bool, dtau
         (n, R) after each frame), and with `measure` the (n, R, 4) sums S1, S2,
         S4, NN of each replica's field after the frame's verdict (the frame's
-        start field again after a rollback)."""
+        start field again after a rollback).  `correlate`: one correlator
+        measurement of the adopted field after every stable frame of a replica
+        (a rolled-back frame measures nothing); the return values are unchanged."""
         n = int(n)
         st = np.zeros((max(n, 0), self.R), dtype=np.int32)
         dt = np.zeros((max(n, 0), self.R))
         ser = np.zeros((max(n, 0), self.R, 4)) if measure else None
-        _lib.call("sq_phi4_ens_run_frames", self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
+        _lib.call("sq_phi4_ens_run_frames_corr" if correlate else "sq_phi4_ens_run_frames", self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
                   None if ser is None else _dptr(ser))
         if n > 0:
             self._frames_run = True
@@ -718,6 +729,63 @@ class Phi4Ensemble:
         out = np.empty((max(k, 0), 5))
         _lib.call("sq_phi4_ens_moments", self._h, int(first), k, _dptr(out))
         return {n: out[:, i].copy() for i, n in enumerate(("S1", "S2", "S4", "NN", "maxabs"))}
+
+    @property
+    def nt(self):
+        """Correlator distances kept: t = 0 .. Lz // 2."""
+        return self.shape[2] // 2 + 1
+
+    def corr_sums(self, first=0, count=None):
+        """The raw correlator accumulators of replicas first .. first + count:
+        (G (count, nt) = Σ over measurements of g(t) = Σ_z S(z) S((z + t) mod Lz),
+        S1 (count,) = Σ of Σ_z S(z), nmeas (count,) int64), S(z) the slice sums
+        Σ_{x,y} φ; see include/stochquant.h for the summation order."""
+        k = self._count(first, count)
+        G = np.zeros((max(k, 0), self.nt))
+        S1 = np.zeros(max(k, 0))
+        nm = np.zeros(max(k, 0), dtype=np.int64)
+        _lib.call("sq_phi4_ens_corr_sums", self._h, int(first), k, _dptr(G), _dptr(S1),
+                  nm.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return G, S1, nm
+
+    def corr_reset(self, first=0, count=None):
+        """Zero the correlator accumulators of replicas first .. first + count (nothing else clears them)."""
+        _lib.call("sq_phi4_ens_corr_reset", self._h, int(first), self._count(first, count))
+
+    def slices(self, first=0, count=None):
+        """One correlator measurement of the current fields, accumulating
+        nothing: (S (count, Lz) slice sums, g (count, nt))."""
+        k = self._count(first, count)
+        S = np.zeros((max(k, 0), self.shape[2]))
+        g = np.zeros((max(k, 0), self.nt))
+        _lib.call("sq_phi4_ens_slices", self._h, int(first), k, _dptr(S), _dptr(g))
+        return S, g
+
+    def correlator(self, n=None, connected=True):
+        """(mean (n,), err (n,), used): over the replicas with at least one
+        measurement, in index order, the mean of c_r(t) = G_r(t) / (nmeas_r V)
+        (minus (S1_r / nmeas_r)² / (Lz V) when `connected`) and its standard
+        error sqrt(Σ (c_r − mean)² / (used (used − 1))), 0 for one replica;
+        n defaults to nt = Lz // 2 + 1.  Raises StochQuantError (SQ_E_STATE)
+        when no replica has a measurement."""
+        n = self.nt if n is None else int(n)
+        mean, err = np.zeros(max(n, 0)), np.zeros(max(n, 0))
+        used = ctypes.c_int(0)
+        _lib.call("sq_phi4_ens_correlator", self._h, 1 if connected else 0, _dptr(mean), _dptr(err), n,
+                  ctypes.byref(used))
+        return mean, err, used.value
+
+    @staticmethod
+    def corr_shape_info(shape):
+        """The correlator launches' LDS layout for a lattice of `shape`
+        (sq_phi4_ens_corr_shape_info; no device needed): {"images" / "lds_bytes"
+        of the step launch with the correlator, "frames_images" /
+        "frames_lds_bytes", "slices_lds_bytes", "nt"}."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 6)()
+        _lib.call("sq_phi4_ens_corr_shape_info", dims, out)
+        return dict(zip(("images", "lds_bytes", "frames_images", "frames_lds_bytes", "slices_lds_bytes", "nt"),
+                        (int(v) for v in out)))
 
     def flags(self, clear=False, first=0, count=None):
         """(count,) bool array: a step since the last clear clamped a site or met a NaN."""
