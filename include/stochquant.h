@@ -482,6 +482,93 @@ int sq_phi4_ens_slices(sq_phi4_ens *e, int first, int count, double *S, double *
 int sq_phi4_ens_correlator(sq_phi4_ens *e, int connected, double *mean, double *err, int n, int *used);
 int sq_phi4_ens_corr_shape_info(const int dims[3], int out[6]);
 
+/* The same correlator projected on spatial momenta p = (2 pi nx / Lx, 2 pi ny /
+ * Ly): C(p, t) = < sum_z Re S_p(z) S_p*(z + t) > / V with S_p(z) = sum_{x,y}
+ * phi(x, y, z) e^{i (px x + py y)} = A(z) + i B(z).  Up to
+ * SQ_PHI4_ENS_MAX_MOMENTA momenta are set on the handle and measured together,
+ * in flight, into accumulators of their own; V, nt as above.
+ *
+ * Twiddle tables: sq_phi4_ens_momentum_table(L, n, c, s) (host only, no handle,
+ * no device) fills, for k = 0 .. L - 1 with j = (n k) mod L, c[k] = cos(a) and
+ * s[k] = sin(a) of the host libm at the double a = 2.0 * M_PI * (double)j /
+ * (double)L, except where 4 j is a multiple of L: there (c, s) is exactly
+ * (1, 0), (0, 1), (-1, 0) or (0, -1).  SQ_E_ARG for L < 2, n outside [0, L) or a
+ * null pointer.  The kernels use exactly these tables (cx, sx of (Lx, nx) and
+ * cy, sy of (Ly, ny)), uploaded when the momenta are set.
+ *
+ * sq_phi4_ens_set_momenta: M pairs nxy[m] = {nx, ny}, 0 <= M <=
+ * SQ_PHI4_ENS_MAX_MOMENTA, 0 <= nx < Lx, 0 <= ny < Ly, duplicates allowed; a
+ * new handle has M = 0.  Every call, with the same list too, zeroes the
+ * momentum accumulators of every replica (their layout depends on M); nothing
+ * else clears them but sq_phi4_ens_pcorr_reset.  SQ_E_ARG for a bad argument
+ * and, whatever M, for a lattice shape the momentum launches cannot hold (see
+ * sq_phi4_ens_pcorr_shape_info).  sq_phi4_ens_get_momenta: *M and, nxy given,
+ * the M pairs (room for SQ_PHI4_ENS_MAX_MOMENTA pairs).
+ *
+ * Projections of slice z for momentum m, in double from the fp32 field: the
+ * slice's float4 quads are dealt to 64 lanes exactly as for S(z) above (x
+ * fastest, then y; lane l takes quads l, l + 64, ... in ascending order).  Quad
+ * i holds the sites x0 .. x0 + 3 of row y, y = i / (Lx / 4), x0 = 4 (i mod (Lx /
+ * 4)), values p0 .. p3.  Per quad, every product and every sum rounded once to
+ * double (no fused multiply-add):
+ *   re = (p0 cx[x0] + p1 cx[x0+1]) + (p2 cx[x0+2] + p3 cx[x0+3])
+ *   im = (p0 sx[x0] + p1 sx[x0+1]) + (p2 sx[x0+2] + p3 sx[x0+3])
+ *   a  = a + (re cy[y] - im sy[y])
+ *   b  = b + (re sy[y] + im cy[y])
+ * a and b from 0.0; the 64 lane values of a, and of b, are combined by the
+ * scan sequence stated for S; lane 63 holds A_m(z) and B_m(z).  The bits depend
+ * on the slice's shape and sites only.  For a finite field, A of momentum
+ * (0, 0) is S(z) bit for bit and B is +0.0.
+ *
+ * One measurement: g_m(t) = sum_{z=0}^{Lz-1} [A(z) A(zt) + B(z) B(zt)], zt = (z
+ * + t) mod Lz, t = 0 .. nt - 1, z ascending from acc = 0.0 as acc = (acc +
+ * A(z) A(zt)) + B(z) B(zt), every product and every sum rounded once; not
+ * divided by V.  For (0, 0) this is g(t) above bit for bit.
+ *
+ * Accumulators, per replica, in device memory, persistent across calls:
+ * Gp[M][nt] doubles and one 64-bit nmeas_p, independent of the zero-momentum
+ * G, S1, nmeas.  A measurement does Gp[m][t] = Gp[m][t] + g_m(t) and nmeas_p +=
+ * 1, so calls split in any way add up to the same bits.
+ *
+ * sq_phi4_ens_step_pcorr: as sq_phi4_ens_step(e, nsteps, every, series) for
+ * fields, counters, flags and series (series nullable); additionally one
+ * momentum measurement after each every-th step (every < 1: SQ_E_ARG; M = 0:
+ * SQ_E_STATE; an incomplete tail measures nothing).  correlate != 0: G, S1 and
+ * nmeas advance as well, exactly as sq_phi4_ens_step_corr would advance them.
+ * sq_phi4_ens_run_frames_pcorr: as sq_phi4_ens_run_frames in everything;
+ * additionally one measurement of the adopted field after every STABLE frame
+ * of a replica (a rolled-back frame measures nothing), and with correlate != 0
+ * what sq_phi4_ens_run_frames_corr adds.  sq_phi4_ens_pcorr_sums: G count rows
+ * of [M][nt], nmeas count entries; either may be NULL.
+ * sq_phi4_ens_pcorr_reset zeroes the range's accumulators.
+ * sq_phi4_ens_pslices: one measurement of the CURRENT fields, accumulating
+ * nothing: AB count rows of [M][Lz][2] = {A, B}, g count rows of [M][nt];
+ * either may be NULL (M = 0: SQ_E_STATE).  sq_phi4_ens_pcorrelator: for each
+ * momentum the statistics of sq_phi4_ens_correlator in its unconnected form
+ * over the replicas with nmeas_p > 0 (none, or M = 0: SQ_E_STATE), c_r(m, t) =
+ * Gp_r[m][t] / (nmeas_p,r V): mean and err rows of n <= nt per momentum.
+ * sq_phi4_ens_pcorr_shape_info (no device, no handle): out = {LDS images and
+ * dynamic LDS bytes of the step launch with momenta, the same two of the
+ * frames launch, LDS bytes of the pslices launch, nt}.  The layout is the
+ * correlator launches' with 2 Lz doubles instead of Lz behind the scratch (S,
+ * then each momentum's A and B in turn: the need does not depend on M); two
+ * images exactly when they fit.  SQ_E_ARG as sq_phi4_ens_shape_info, and where
+ * one image, a launch's scratch and 16 Lz bytes exceed the 160 KiB of LDS in
+ * any of the three launches: (8, 2, 2048) is refused, (8, 2, 2000) is not. */
+#define SQ_PHI4_ENS_MAX_MOMENTA 8
+int sq_phi4_ens_momentum_table(int L, int n, double *c, double *s);
+int sq_phi4_ens_set_momenta(sq_phi4_ens *e, int M, const int *nxy /*[M][2] = nx, ny*/);
+int sq_phi4_ens_get_momenta(sq_phi4_ens *e, int *M, int *nxy);
+int sq_phi4_ens_step_pcorr(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate);
+int sq_phi4_ens_run_frames_pcorr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series,
+                                 int correlate);
+int sq_phi4_ens_pcorr_sums(sq_phi4_ens *e, int first, int count, double *G /*[count][M][nt]*/, long long *nmeas);
+int sq_phi4_ens_pcorr_reset(sq_phi4_ens *e, int first, int count);
+int sq_phi4_ens_pslices(sq_phi4_ens *e, int first, int count, double *AB /*[count][M][Lz][2]*/,
+                        double *g /*[count][M][nt]*/);
+int sq_phi4_ens_pcorrelator(sq_phi4_ens *e, double *mean /*[M][n]*/, double *err, int n, int *used);
+int sq_phi4_ens_pcorr_shape_info(const int dims[3], int out[6]);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

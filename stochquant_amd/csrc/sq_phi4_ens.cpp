@@ -43,6 +43,14 @@ struct sq_phi4_ens {
     long long *cN = nullptr;             // [R]
     double *ctmp = nullptr;              // sq_phi4_ens_slices' device buffer: [count][Lz] then [count][nt]
     size_t ctmp_cap = 0;                 // ... in replicas
+    int pM = 0;                          // momenta set (sq_phi4_ens_set_momenta), 0 .. SQ_PHI4_ENS_MAX_MOMENTA
+    int pn[2 * SQ_PHI4_ENS_MAX_MOMENTA] = {};  // their (nx, ny)
+    double *ptab = nullptr;              // twiddle tables: cx | sx [8][Lx], cy | sy [8][Ly] (first set_momenta on)
+    double *pG = nullptr;                // [R][pM][nt] momentum accumulators: zeroed by set_momenta and
+    long long *pN = nullptr;             // [R]         sq_phi4_ens_pcorr_reset only
+    size_t pG_cap = 0;                   // ... in momenta
+    double *ptmp = nullptr;              // sq_phi4_ens_pslices' device buffer: [count][pM][Lz][2] then [count][pM][nt]
+    size_t ptmp_cap = 0;                 // ... in doubles
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -133,6 +141,13 @@ void release_phi4_ens(sq_phi4_ens *e) {
     (void)hipFree(e->cS1);
     (void)hipFree(e->cN);
     (void)hipFree(e->ctmp);
+    (void)hipFree(e->ptab);
+    (void)hipFree(e->pG);
+    (void)hipFree(e->pN);
+    (void)hipFree(e->ptmp);
+    e->ptab = e->pG = e->ptmp = nullptr;
+    e->pN = nullptr;
+    e->pG_cap = e->ptmp_cap = 0;
     e->cG = e->cS1 = e->ctmp = nullptr;
     e->cN = nullptr;
     e->ctmp_cap = 0;
@@ -156,8 +171,24 @@ sq::Phi4EnsCorrArgs ens_corr_args(const sq_phi4_ens *e) {
     return c;
 }
 
-// sq_phi4_ens_step (corr = false) and sq_phi4_ens_step_corr (corr = true; every >= 1 checked by the caller)
-int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr) {
+// The handle's momenta for a launch; corr: the zero-momentum accumulators advance as well.
+sq::Phi4EnsPCorrArgs ens_pcorr_args(const sq_phi4_ens *e, bool corr) {
+    sq::Phi4EnsPCorrArgs p{};
+    const size_t nx = (size_t)SQ_PHI4_ENS_MAX_MOMENTA * (size_t)e->Lx, ny = (size_t)SQ_PHI4_ENS_MAX_MOMENTA * (size_t)e->Ly;
+    p.Gp = e->pG;
+    p.nmeas_p = e->pN;
+    p.cx = e->ptab;
+    p.sx = e->ptab + nx;
+    p.cy = e->ptab + 2 * nx;
+    p.sy = e->ptab + 2 * nx + ny;
+    p.M = e->pM;
+    if (corr) p.corr = ens_corr_args(e);
+    return p;
+}
+
+// sq_phi4_ens_step (corr = false), sq_phi4_ens_step_corr (corr = true) and sq_phi4_ens_step_pcorr (pcorr = true,
+// corr its `correlate`); with either measurement every >= 1, checked by the caller
+int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr, bool pcorr = false) {
     if (nsteps == 0) return SQ_OK;
     DeviceGuard g(e->dev);
     int rc = ens_sync_recs(e);
@@ -176,9 +207,10 @@ int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr) {
     }
     sq::Phi4EnsArgs a = ens_args(e);
     a.nsteps = nsteps;
-    a.every = (nd || corr) ? every : 0;
+    a.every = (nd || corr || pcorr) ? every : 0;
     a.series = nd ? e->series : nullptr;
-    if (corr) SQ_HIP(sq::phi4_ens_step_corr_launch(a, ens_corr_args(e), e->R, e->stream));
+    if (pcorr) SQ_HIP(sq::phi4_ens_step_pcorr_launch(a, ens_pcorr_args(e, corr), e->R, e->stream));
+    else if (corr) SQ_HIP(sq::phi4_ens_step_corr_launch(a, ens_corr_args(e), e->R, e->stream));
     else SQ_HIP(sq::phi4_ens_step_launch(a, e->R, e->stream));
     e->launches++;
     SQ_HIP(hipStreamSynchronize(e->stream));
@@ -237,6 +269,8 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         SQ_HIP(hipMemset(e->cG, 0, sizeof(double) * (size_t)e->nt * (size_t)nrep));
         SQ_HIP(hipMemset(e->cS1, 0, sizeof(double) * (size_t)nrep));
         SQ_HIP(hipMemset(e->cN, 0, sizeof(long long) * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->pN, sizeof(long long) * (size_t)nrep));
+        SQ_HIP(hipMemset(e->pN, 0, sizeof(long long) * (size_t)nrep));
         SQ_HIP(hipMemset(e->field, 0, bytes));
         SQ_HIP(hipMemset(e->flags, 0, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -374,7 +408,8 @@ int sq_phi4_ens_step_corr(sq_phi4_ens *e, int nsteps, int every, double *series)
 }
 
 namespace {
-int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr);
+int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr,
+                   bool pcorr = false);
 }
 
 int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
@@ -389,10 +424,11 @@ int sq_phi4_ens_run_frames_corr(sq_phi4_ens *e, int nframes, int *stable, double
 
 namespace {
 
-int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr) {
+int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr, bool pcorr) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
     if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
+    if (pcorr && e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
     if (nframes == 0) return SQ_OK;
     if (!stable || !dtau) return fail(SQ_E_ARG, "null argument");
     DeviceGuard g(e->dev);
@@ -439,7 +475,8 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
     f.nframes = nframes;
     f.loops = L;
     f.adapt = e->p.adapt_dtau ? 1 : 0;
-    if (corr) SQ_HIP(sq::phi4_ens_frames_corr_launch(a, f, ens_corr_args(e), e->R, e->stream));
+    if (pcorr) SQ_HIP(sq::phi4_ens_frames_pcorr_launch(a, f, ens_pcorr_args(e, corr), e->R, e->stream));
+    else if (corr) SQ_HIP(sq::phi4_ens_frames_corr_launch(a, f, ens_corr_args(e), e->R, e->stream));
     else SQ_HIP(sq::phi4_ens_frames_launch(a, f, e->R, e->stream));
     e->launches++;
     SQ_HIP(hipMemcpyAsync(e->fst.data(), e->fst_dev, sizeof(sq::Phi4EnsFrameState) * R, hipMemcpyDeviceToHost,
@@ -455,6 +492,38 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
     }
     e->rec_dirty = true;  // Δτ and the counters moved
     return SQ_OK;
+}
+
+// Replica statistics of one accumulator row (sq_phi4_ens_correlator, sq_phi4_ens_pcorrelator): replica r's
+// entries at G[r * stride + t], t < n; the u replicas with N[r] > 0 in index order; S1 non-null: the connected
+// form.  err nullable.
+void ens_replica_stats(const sq_phi4_ens *e, const double *G, size_t stride, const double *S1, const long long *N,
+                       int u, int n, double *mean, double *err) {
+    const size_t R = (size_t)e->R;
+    const double V = (double)e->sites, Lz = (double)e->Lz;
+    std::vector<double> c((size_t)u);
+    for (int t = 0; t < n; ++t) {
+        size_t k = 0;
+        double sum = 0.0;
+        for (size_t r = 0; r < R; ++r) {
+            if (N[r] <= 0) continue;
+            const double nm = (double)N[r];
+            double v = G[r * stride + (size_t)t] / (nm * V);
+            if (S1) {
+                const double sb = S1[r] / nm;
+                v -= sb * sb / (Lz * V);
+            }
+            c[k++] = v;
+            sum += v;
+        }
+        const double m = sum / (double)u;
+        mean[t] = m;
+        if (err) {
+            double q = 0.0;
+            for (int i = 0; i < u; ++i) q += (c[(size_t)i] - m) * (c[(size_t)i] - m);
+            err[t] = u > 1 ? sqrt(q / ((double)u * (double)(u - 1))) : 0.0;
+        }
+    }
 }
 
 }  // namespace
@@ -520,30 +589,163 @@ int sq_phi4_ens_correlator(sq_phi4_ens *e, int connected, double *mean, double *
     for (size_t r = 0; r < R; ++r) u += N[r] > 0 ? 1 : 0;
     if (used) *used = u;
     if (u == 0) return fail(SQ_E_STATE, "no replica has a correlator measurement");
-    const double V = (double)e->sites, Lz = (double)e->Lz;
-    std::vector<double> c((size_t)u);
-    for (int t = 0; t < n; ++t) {
-        size_t k = 0;
-        double sum = 0.0;
-        for (size_t r = 0; r < R; ++r) {
-            if (N[r] <= 0) continue;
-            const double nm = (double)N[r];
-            double v = G[r * nt + (size_t)t] / (nm * V);
-            if (connected) {
-                const double sb = S1[r] / nm;
-                v -= sb * sb / (Lz * V);
-            }
-            c[k++] = v;
-            sum += v;
-        }
-        const double m = sum / (double)u;
-        mean[t] = m;
-        if (err) {
-            double q = 0.0;
-            for (int i = 0; i < u; ++i) q += (c[(size_t)i] - m) * (c[(size_t)i] - m);
-            err[t] = u > 1 ? sqrt(q / ((double)u * (double)(u - 1))) : 0.0;
+    ens_replica_stats(e, G.data(), nt, connected ? S1.data() : nullptr, N.data(), u, n, mean, err);
+    return SQ_OK;
+}
+
+int sq_phi4_ens_momentum_table(int L, int n, double *c, double *s) {
+    if (L < 2 || n < 0 || n >= L) return fail(SQ_E_ARG, "a momentum table needs L >= 2 and 0 <= n < L");
+    if (!c || !s) return fail(SQ_E_ARG, "null argument");
+    for (int k = 0; k < L; ++k) {
+        const long long j = ((long long)n * (long long)k) % (long long)L;
+        if ((4 * j) % L == 0) {  // a multiple of a quarter turn: exact
+            const int q = (int)(4 * j / L);
+            c[k] = q == 0 ? 1.0 : (q == 2 ? -1.0 : 0.0);
+            s[k] = q == 1 ? 1.0 : (q == 3 ? -1.0 : 0.0);
+        } else {
+            const double a = 2.0 * M_PI * (double)j / (double)L;
+            c[k] = cos(a);
+            s[k] = sin(a);
         }
     }
+    return SQ_OK;
+}
+
+int sq_phi4_ens_set_momenta(sq_phi4_ens *e, int M, const int *nxy) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (M < 0 || M > SQ_PHI4_ENS_MAX_MOMENTA) return fail(SQ_E_ARG, "0 <= M <= SQ_PHI4_ENS_MAX_MOMENTA momenta");
+    if (M > 0 && !nxy) return fail(SQ_E_ARG, "null argument");
+    for (int m = 0; m < M; ++m)
+        if (nxy[2 * m] < 0 || nxy[2 * m] >= e->Lx || nxy[2 * m + 1] < 0 || nxy[2 * m + 1] >= e->Ly)
+            return fail(SQ_E_ARG, "a momentum needs 0 <= nx < Lx and 0 <= ny < Ly");
+    if (!sq::phi4_ens_shape((int)e->sites, e->Lz).pc_ok)
+        return fail(SQ_E_ARG, "the lattice shape leaves no LDS for the momentum projections (16 Lz bytes)");
+    DeviceGuard g(e->dev);
+    const size_t Lx = (size_t)e->Lx, Ly = (size_t)e->Ly, R = (size_t)e->R, nt = (size_t)e->nt;
+    const size_t nx = SQ_PHI4_ENS_MAX_MOMENTA * Lx, ny = SQ_PHI4_ENS_MAX_MOMENTA * Ly;
+    if (!e->ptab) SQ_HIP(hipMalloc(&e->ptab, sizeof(double) * 2 * (nx + ny)));
+    if ((size_t)M > e->pG_cap) {
+        (void)hipFree(e->pG);
+        e->pG = nullptr;
+        e->pG_cap = 0;
+        SQ_HIP(hipMalloc(&e->pG, sizeof(double) * R * (size_t)M * nt));
+        e->pG_cap = (size_t)M;
+    }
+    std::vector<double> tab(2 * (nx + ny), 0.0);
+    for (int m = 0; m < M; ++m) {
+        int rc = sq_phi4_ens_momentum_table(e->Lx, nxy[2 * m], &tab[(size_t)m * Lx], &tab[nx + (size_t)m * Lx]);
+        if (!rc)
+            rc = sq_phi4_ens_momentum_table(e->Ly, nxy[2 * m + 1], &tab[2 * nx + (size_t)m * Ly],
+                                            &tab[2 * nx + ny + (size_t)m * Ly]);
+        if (rc) return rc;
+    }
+    SQ_HIP(hipMemcpy(e->ptab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    e->pM = M;  // the accumulators' layout is [R][M][nt] from here on: all of them start over
+    for (int i = 0; i < 2 * M; ++i) e->pn[i] = nxy[i];
+    if (M > 0) SQ_HIP(hipMemsetAsync(e->pG, 0, sizeof(double) * R * (size_t)M * nt, e->stream));
+    SQ_HIP(hipMemsetAsync(e->pN, 0, sizeof(long long) * R, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_get_momenta(sq_phi4_ens *e, int *M, int *nxy) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (!M) return fail(SQ_E_ARG, "null argument");
+    *M = e->pM;
+    if (nxy)
+        for (int i = 0; i < 2 * e->pM; ++i) nxy[i] = e->pn[i];
+    return SQ_OK;
+}
+
+int sq_phi4_ens_step_pcorr(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (every < 1) return fail(SQ_E_ARG, "a momentum measurement needs every >= 1");
+    if (e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
+    return ens_step(e, nsteps, every, series, correlate != 0, true);
+}
+
+int sq_phi4_ens_run_frames_pcorr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series,
+                                 int correlate) {
+    return ens_run_frames(e, nframes, stable, dtau, series, correlate != 0, true);
+}
+
+int sq_phi4_ens_pcorr_sums(sq_phi4_ens *e, int first, int count, double *G, long long *nmeas) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t row = (size_t)e->pM * (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    if (G && row) SQ_HIP(hipMemcpy(G, e->pG + f * row, sizeof(double) * n * row, hipMemcpyDeviceToHost));
+    if (nmeas) SQ_HIP(hipMemcpy(nmeas, e->pN + f, sizeof(long long) * n, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_pcorr_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t row = (size_t)e->pM * (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    if (row) SQ_HIP(hipMemsetAsync(e->pG + f * row, 0, sizeof(double) * n * row, e->stream));
+    SQ_HIP(hipMemsetAsync(e->pN + f, 0, sizeof(long long) * n, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_pslices(sq_phi4_ens *e, int first, int count, double *AB, double *g) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
+    if (count == 0 || (!AB && !g)) return SQ_OK;
+    DeviceGuard dg(e->dev);
+    const size_t nab = (size_t)count * (size_t)e->pM * 2 * (size_t)e->Lz, ng = (size_t)count * (size_t)e->pM * (size_t)e->nt;
+    if (nab + ng > e->ptmp_cap) {
+        (void)hipFree(e->ptmp);
+        e->ptmp = nullptr;
+        e->ptmp_cap = 0;
+        SQ_HIP(hipMalloc(&e->ptmp, sizeof(double) * (nab + ng)));
+        e->ptmp_cap = nab + ng;
+    }
+    double *devAB = e->ptmp, *devg = e->ptmp + nab;
+    SQ_HIP(sq::phi4_ens_pslices_launch(ens_args(e), ens_pcorr_args(e, false), first, count, devAB, devg, e->stream));
+    if (AB) SQ_HIP(hipMemcpyAsync(AB, devAB, sizeof(double) * nab, hipMemcpyDeviceToHost, e->stream));
+    if (g) SQ_HIP(hipMemcpyAsync(g, devg, sizeof(double) * ng, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_pcorrelator(sq_phi4_ens *e, double *mean, double *err, int n, int *used) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (n < 0 || n > e->nt) return fail(SQ_E_ARG, "n must lie in [0, Lz / 2 + 1]");
+    if (!mean && n > 0) return fail(SQ_E_ARG, "null argument");
+    if (e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
+    const size_t R = (size_t)e->R, nt = (size_t)e->nt, M = (size_t)e->pM;
+    std::vector<double> G(R * M * nt);
+    std::vector<long long> N(R);
+    int rc = sq_phi4_ens_pcorr_sums(e, 0, e->R, G.data(), N.data());
+    if (rc) return rc;
+    int u = 0;
+    for (size_t r = 0; r < R; ++r) u += N[r] > 0 ? 1 : 0;
+    if (used) *used = u;
+    if (u == 0) return fail(SQ_E_STATE, "no replica has a momentum measurement");
+    for (size_t m = 0; m < M; ++m)
+        ens_replica_stats(e, G.data() + m * nt, M * nt, nullptr, N.data(), u, n, mean + m * (size_t)n,
+                          err ? err + m * (size_t)n : nullptr);
+    return SQ_OK;
+}
+
+int sq_phi4_ens_pcorr_shape_info(const int dims[3], int out[6]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
+    if (!s.pc_ok) return fail(SQ_E_ARG, "the lattice shape leaves no LDS for the momentum projections (16 Lz bytes)");
+    out[0] = s.pc_two ? 2 : 1;
+    out[1] = s.pc_lds_bytes;
+    out[2] = s.pc_fr_two ? 2 : 1;
+    out[3] = s.pc_fr_lds_bytes;
+    out[4] = s.pc_sl_lds_bytes;
+    out[5] = dims[2] / 2 + 1;
     return SQ_OK;
 }
 

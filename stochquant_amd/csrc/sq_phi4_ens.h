@@ -72,6 +72,21 @@ struct Phi4EnsCorrArgs {
     long long *nmeas;   // [R]
 };
 
+constexpr int kPhi4EnsMaxMomenta = 8;  // SQ_PHI4_ENS_MAX_MOMENTA
+
+// The momentum-projected correlator: per replica Gp[m][t] += g_m(t) for the M momenta set
+// on the handle and nmeas_p += 1 per measurement.  The twiddle tables are one row per momentum (row m the
+// table of n_x / n_y of momentum m, sq_phi4_ens_momentum_table's values), so the kernels need no list of the
+// momenta themselves.  corr.G non-null: the zero-momentum accumulators advance as well (`correlate`).
+struct Phi4EnsPCorrArgs {
+    double *Gp;              // [R][M][nt]
+    long long *nmeas_p;      // [R]
+    const double *cx, *sx;   // [M][Lx]
+    const double *cy, *sy;   // [M][Ly]
+    int M;                   // 1 .. kPhi4EnsMaxMomenta
+    Phi4EnsCorrArgs corr;    // nullable (G == nullptr)
+};
+
 // Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
 // quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and per
 // launch whether two LDS images fit (one barrier per step instead of two) and
@@ -91,6 +106,14 @@ struct Phi4EnsShape {
     bool co_fr_two;     // the frames launch with the correlator
     int co_fr_lds_bytes;
     int sl_lds_bytes;   // the slices launch: one image, the scratch, the slice sums
+    // the momentum launches (Lz > 0): the correlator launches' layouts with 2 Lz doubles behind the scratch
+    // (S, then each momentum's A and B in turn: the need does not depend on the number of momenta)
+    bool pc_ok;         // one image fits in all three launches: the shape can hold momenta
+    bool pc_two;        // the step launch with momenta
+    int pc_lds_bytes;
+    bool pc_fr_two;     // the frames launch with momenta
+    int pc_fr_lds_bytes;
+    int pc_sl_lds_bytes;  // the pslices launch: one image, the scratch, the projections
 };
 Phi4EnsShape phi4_ens_shape(int sites, int Lz = 0);
 
@@ -107,6 +130,16 @@ hipError_t phi4_ens_frames_corr_launch(const Phi4EnsArgs &a, const Phi4EnsFrameA
 // One measurement of the stored fields of replicas first .. first + count, accumulating nothing:
 // S[r][Lz] slice sums, g[r][nt] (device memory, both non-null).
 hipError_t phi4_ens_slices_launch(const Phi4EnsArgs &a, int first, int count, double *S, double *g, hipStream_t s);
+// The step and frames launches with one momentum measurement (ens_pcorr) where the correlator launches take
+// theirs, after the sums and after the zero-momentum measurement when p.corr is given.  A shape that cannot
+// hold momenta (Phi4EnsShape::pc_ok) is hipErrorInvalidValue.
+hipError_t phi4_ens_step_pcorr_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs &p, int nrep, hipStream_t s);
+hipError_t phi4_ens_frames_pcorr_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsPCorrArgs &p,
+                                        int nrep, hipStream_t s);
+// One momentum measurement of the stored fields of replicas first .. first + count, accumulating nothing:
+// AB[r][M][Lz][2] projections, g[r][M][nt] (device memory, both non-null); p.Gp, p.nmeas_p, p.corr are not used.
+hipError_t phi4_ens_pslices_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs &p, int first, int count, double *AB,
+                                   double *g, hipStream_t s);
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

@@ -36,8 +36,12 @@
 // The correlator instances of both kernels add ens_corr, the zero-momentum
 // time-slice correlator over z of the field in the image, accumulated per
 // replica in device memory; phi4_ens_slices_kernel is the same routine on the
-// stored field.
+// stored field.  The momentum instances add ens_pcorr, the same correlator
+// projected on spatial momenta (p_x, p_y); phi4_ens_pslices_kernel is that
+// routine on the stored field.
 #define SQ_PHI4_KERNELS_ONLY
+#include <type_traits>
+
 #include "sq_phi4.hip"
 #include "sq_phi4_ens.h"
 
@@ -245,6 +249,89 @@ __device__ __forceinline__ void ens_corr(const EnsGeo &g, int Lz, const float *i
     }
 }
 
+// One momentum measurement of the field in img, momentum by
+// momentum through the 2 Lz doubles at Pl (A at Pl[z], B at Pl[Lz + z]; the
+// zero-momentum Sl of an ens_corr call just before lies in the same region).
+// Projections: as ens_corr's slice sums, wave w slices w, w + nw, ..., the
+// lanes striding the slice's quads; 64 is a multiple of the row's quads, so
+// every quad of a lane has the same x0 = 4 (lane mod qrow) and its eight
+// x-twiddles are loaded once per momentum; the row y = i / qrow changes per
+// quad.  Per quad re = (p0 cx0 + p1 cx1) + (p2 cx2 + p3 cx3), im the same with
+// sx, a += re cy - im sy, b += re sy + im cy, every product and sum rounded
+// once; the wave by ens_wave_sum.  Then, behind a barrier, lane t (and t + T)
+// forms g_m(t) = sum_z [A(z) A(zt) + B(z) B(zt)] as (acc + A A) + B B, z
+// ascending.  ACC: Gp[m][t] = Gp[m][t] + g_m(t) and nmeas_p += 1 in place (the
+// same lane owns an entry for the whole call); else Gp[m][t] = g_m(t) and, ABout
+// given, the projections to ABout[m][z][2].  A barrier stands between a
+// region's last reader and its next writer: at the top of every momentum (the
+// reader before the first one is ens_corr's or the previous measurement's).
+// Every lane of the block calls it; Pl is free again after the next block barrier.
+template <bool ACC>
+__device__ __forceinline__ void ens_pcorr(const EnsGeo &g, int Ly, int Lz, const float *img, double *Pl,
+                                          const Phi4EnsPCorrArgs &P, double *Gp, long long *nm, double *ABout) {
+#pragma clang fp contract(off)
+    const float4 *img4 = reinterpret_cast<const float4 *>(img);
+    // opaque per measurement: nothing that depends on the lane is hoisted out of the caller's loops and kept
+    // in registers across its steps (the K = 8 frames instance has none to spare)
+    int tid = (int)threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int T = blockDim.x, lane = tid & 63, nw = T >> 6;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nt = Lz / 2 + 1;
+    const int qsh = 31 - __builtin_clz((unsigned)g.qrow);  // qrow is a power of two
+    const int x0 = 4 * (lane & (g.qrow - 1));
+    double *Al = Pl, *Bl = Pl + Lz;
+    for (int m = 0; m < P.M; ++m) {
+        const double *cx = P.cx + m * g.Lx + x0, *sx = P.sx + m * g.Lx + x0;
+        const double *cy = P.cy + m * Ly, *sy = P.sy + m * Ly;
+        const double c0 = cx[0], c1 = cx[1], c2 = cx[2], c3 = cx[3];
+        const double s0 = sx[0], s1 = sx[1], s2 = sx[2], s3 = sx[3];
+        __syncthreads();
+        for (int z = w; z < Lz; z += nw) {  // wave-uniform: every lane reaches the scans
+            const float4 *sl = img4 + z * g.qplane;
+            double a = 0.0, b = 0.0;
+            for (int i = lane; i < g.qplane; i += 64) {
+                const float4 v = sl[i];
+                const int y = i >> qsh;
+                const double p0 = v.x, p1 = v.y, p2 = v.z, p3 = v.w, yc = cy[y], ys = sy[y];
+                const double re = __dadd_rn(__dadd_rn(__dmul_rn(p0, c0), __dmul_rn(p1, c1)),
+                                            __dadd_rn(__dmul_rn(p2, c2), __dmul_rn(p3, c3)));
+                const double im = __dadd_rn(__dadd_rn(__dmul_rn(p0, s0), __dmul_rn(p1, s1)),
+                                            __dadd_rn(__dmul_rn(p2, s2), __dmul_rn(p3, s3)));
+                a = __dadd_rn(a, __dsub_rn(__dmul_rn(re, yc), __dmul_rn(im, ys)));
+                b = __dadd_rn(b, __dadd_rn(__dmul_rn(re, ys), __dmul_rn(im, yc)));
+            }
+            a = ens_wave_sum(a);
+            b = ens_wave_sum(b);
+            if (lane == 63) {
+                Al[z] = a;
+                Bl[z] = b;
+            }
+        }
+        __syncthreads();
+        double *G = Gp + m * nt;
+        for (int t = tid; t < nt; t += T) {
+            double old = 0.0;
+            if (ACC) old = G[t];
+            double acc = 0.0;
+            int zt = t;
+            for (int z = 0; z < Lz; ++z) {
+                acc = __dadd_rn(__dadd_rn(acc, __dmul_rn(Al[z], Al[zt])), __dmul_rn(Bl[z], Bl[zt]));
+                zt = zt + 1 == Lz ? 0 : zt + 1;
+            }
+            G[t] = ACC ? __dadd_rn(old, acc) : acc;
+        }
+        if (!ACC && ABout != nullptr) {
+            double *o = ABout + (size_t)m * (size_t)(2 * Lz);
+            for (int z = tid; z < Lz; z += T) {
+                o[2 * z] = Al[z];
+                o[2 * z + 1] = Bl[z];
+            }
+        }
+    }
+    if (ACC && tid == T - 1) *nm += 1;
+}
+
 template <int K>
 __device__ __forceinline__ void ens_load(const Phi4EnsArgs &E, const EnsGeo &g, int r, float4 (&c)[K],
                                          uint32_t (&fl)[K], float *img) {
@@ -275,14 +362,35 @@ __device__ __forceinline__ Phi4EnsCorrArgs ens_corr_args(const CA &...c) {
     return a[0];
 }
 
+// The momentum instances are the third kind: CA = {Phi4EnsPCorrArgs}.
+template <typename... CA>
+constexpr bool kEnsPCorr = (std::is_same<CA, Phi4EnsPCorrArgs>::value || ...);
+template <typename... CA>
+__device__ __forceinline__ Phi4EnsPCorrArgs ens_pcorr_args(const CA &...c) {
+    static_assert(sizeof...(CA) <= 1, "at most one Phi4EnsPCorrArgs");
+    const Phi4EnsPCorrArgs a[] = {c..., Phi4EnsPCorrArgs{}};
+    return a[0];
+}
+
+// The replica's momentum measurement where its zero-momentum one sits: that one
+// first when P.corr is given, both through the region at Pl.
+__device__ __forceinline__ void ens_pcorr_measure(const EnsGeo &g, const Phi4EnsArgs &E, int r, const float *img,
+                                                  double *Pl, const Phi4EnsPCorrArgs &P) {
+    const int nt = E.Lz / 2 + 1;
+    if (P.corr.G != nullptr)  // block-uniform
+        ens_corr<true>(g, E.Lz, img, Pl, P.corr.G + (size_t)r * (size_t)nt, P.corr.S1 + r, P.corr.nmeas + r, nullptr);
+    ens_pcorr<true>(g, E.Ly, E.Lz, img, Pl, P, P.Gp + (size_t)r * (size_t)(P.M * nt), P.nmeas_p + r, nullptr);
+}
+
 // two != 0: two LDS images (the launcher sized the dynamic LDS for them).
 // With the correlator: one ens_corr measurement after each every-th step into
 // the replica's rows, the slice sums behind the scratch; the series as without
-// it when E.series is given.
+// it when E.series is given.  With momenta: ens_pcorr_measure in its place.
 template <int K, typename... CA>
 __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const Phi4EnsArgs E, const int two,
                                                                           const CA... ca) {
-    constexpr bool CORR = sizeof...(CA) != 0;
+    constexpr bool PC = kEnsPCorr<CA...>;
+    constexpr bool CORR = sizeof...(CA) != 0;  // either kind of measurement
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
@@ -333,7 +441,9 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const P
                 ens_fold(sm, mx, scr, E.series + 4 * ((size_t)rec * gridDim.x + (size_t)r), false);
                 ++rec;
             }
-            if constexpr (CORR) {
+            if constexpr (PC) {
+                ens_pcorr_measure(g, E, r, cur, scr + kPhi4EnsScratchBytes / 8, ens_pcorr_args(ca...));
+            } else if constexpr (CORR) {
                 const Phi4EnsCorrArgs C = ens_corr_args(ca...);
                 ens_corr<true>(g, E.Lz, cur, scr + kPhi4EnsScratchBytes / 8, C.G + (size_t)r * (size_t)(E.Lz / 2 + 1),
                                C.S1 + r, C.nmeas + r, nullptr);
@@ -418,12 +528,14 @@ __device__ __forceinline__ void ens_step_fr(const Phi4StepArgs &A, const EnsGeo 
 //
 // CORR: one ens_corr measurement of the adopted field after every stable frame
 // (after the verdict: cur holds that field and every wave is past the last
-// step's barrier); a rolled-back frame measures nothing.
+// step's barrier); a rolled-back frame measures nothing.  With momenta:
+// ens_pcorr_measure in its place.
 template <int K, typename... CA>
 __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const Phi4EnsArgs E,
                                                                             const Phi4EnsFrameArgs F, const int two,
                                                                             const CA... ca) {
-    constexpr bool CORR = sizeof...(CA) != 0;
+    constexpr bool PC = kEnsPCorr<CA...>;
+    constexpr bool CORR = sizeof...(CA) != 0;  // either kind of measurement
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
@@ -584,7 +696,11 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const
             ens_sums<K>(g, c, fl, cur, sm, mx);
             ens_fold(sm, mx, scr, E.series + 4 * ((size_t)f * gridDim.x + (size_t)r), false);
         }
-        if constexpr (CORR) {
+        if constexpr (PC) {
+            if (stable)  // block-uniform, as below
+                ens_pcorr_measure(g, E, r, cur, reinterpret_cast<double *>(sb + kPhi4EnsFrameScratchBytes),
+                                  ens_pcorr_args(ca...));
+        } else if constexpr (CORR) {
             if (stable) {  // block-uniform: every lane decided the frame from the same records
                 const Phi4EnsCorrArgs C = ens_corr_args(ca...);
                 ens_corr<true>(g, E.Lz, cur, reinterpret_cast<double *>(sb + kPhi4EnsFrameScratchBytes),
@@ -639,6 +755,23 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_slices_kernel(const
                     S + (size_t)blockIdx.x * (size_t)E.Lz);
 }
 
+// ens_pcorr on the stored field of replica first + blockIdx.x, accumulating
+// nothing: AB[blockIdx.x][M][Lz][2], g[blockIdx.x][M][nt].
+template <int K>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_pslices_kernel(const Phi4EnsArgs E,
+                                                                             const Phi4EnsPCorrArgs P, const int first,
+                                                                             double *AB, double *gout) {
+    const int r = first + blockIdx.x;
+    const EnsGeo g = ens_geo(E);
+    float *img = reinterpret_cast<float *>(ens_smem);
+    double *Pl = reinterpret_cast<double *>(ens_smem + 16 * (size_t)g.Q + kPhi4EnsScratchBytes);
+    float4 c[K];
+    uint32_t fl[K];
+    ens_load<K>(E, g, r, c, fl, img);  // ends in a barrier
+    ens_pcorr<false>(g, E.Ly, E.Lz, img, Pl, P, gout + (size_t)blockIdx.x * (size_t)(P.M * (E.Lz / 2 + 1)), nullptr,
+                     AB + (size_t)blockIdx.x * (size_t)(P.M * 2 * E.Lz));
+}
+
 // phi4_init_kernel's field for every replica (blockIdx.y) from its own key.
 __global__ __launch_bounds__(256) void phi4_ens_init_kernel(const Phi4EnsArgs E, const float amp) {
     const int r = blockIdx.y;
@@ -684,7 +817,83 @@ Phi4EnsShape phi4_ens_shape(int sites, int Lz) {
     s.co_fr_two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes + sl <= kPhi4EnsLdsBytes;
     s.co_fr_lds_bytes = (s.co_fr_two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes + sl;
     s.sl_lds_bytes = 4 * sites + kPhi4EnsScratchBytes + sl;
+    // the momentum launches: 2 Lz doubles there; legal when one image fits in each of the three
+    const int pl = 16 * Lz;
+    s.pc_two = 2 * 4 * sites + kPhi4EnsScratchBytes + pl <= kPhi4EnsLdsBytes;
+    s.pc_lds_bytes = (s.pc_two ? 2 : 1) * 4 * sites + kPhi4EnsScratchBytes + pl;
+    s.pc_fr_two = 2 * 4 * sites + kPhi4EnsFrameScratchBytes + pl <= kPhi4EnsLdsBytes;
+    s.pc_fr_lds_bytes = (s.pc_fr_two ? 2 : 1) * 4 * sites + kPhi4EnsFrameScratchBytes + pl;
+    s.pc_sl_lds_bytes = 4 * sites + kPhi4EnsScratchBytes + pl;
+    s.pc_ok = Lz > 0 && s.pc_lds_bytes <= kPhi4EnsLdsBytes && s.pc_fr_lds_bytes <= kPhi4EnsLdsBytes &&
+              s.pc_sl_lds_bytes <= kPhi4EnsLdsBytes;
     return s;
+}
+
+namespace {
+bool ens_pcorr_ok(const Phi4EnsPCorrArgs &p, bool acc) {
+    return p.cx != nullptr && p.sx != nullptr && p.cy != nullptr && p.sy != nullptr && p.M >= 1 &&
+           p.M <= kPhi4EnsMaxMomenta && (!acc || (p.Gp != nullptr && p.nmeas_p != nullptr)) &&
+           (p.corr.G == nullptr || (p.corr.S1 != nullptr && p.corr.nmeas != nullptr));
+}
+}  // namespace
+
+hipError_t phi4_ens_step_pcorr_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs &p, int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < 1 || !ens_pcorr_ok(p, true))
+        return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    if (!sh.pc_ok) return hipErrorInvalidValue;
+    Phi4EnsArgs q = a;
+    Phi4EnsPCorrArgs pq = p;
+    int two = sh.pc_two ? 1 : 0;
+    void *args[] = {&q, &two, &pq};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_step_kernel<1, Phi4EnsPCorrArgs>
+                     : sh.K == 2 ? (const void *)&phi4_ens_step_kernel<2, Phi4EnsPCorrArgs>
+                     : sh.K == 4 ? (const void *)&phi4_ens_step_kernel<4, Phi4EnsPCorrArgs>
+                                 : (const void *)&phi4_ens_step_kernel<8, Phi4EnsPCorrArgs>;
+    hipError_t e = ens_lds_attr(fn, sh.pc_lds_bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.pc_lds_bytes, s);
+}
+
+hipError_t phi4_ens_frames_pcorr_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsPCorrArgs &p,
+                                        int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
+        f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr || !ens_pcorr_ok(p, true))
+        return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    if (!sh.pc_ok) return hipErrorInvalidValue;
+    int two = sh.pc_fr_two ? 1 : 0;
+    const int bytes = sh.pc_fr_lds_bytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsFrameArgs fq = f;
+    Phi4EnsPCorrArgs pq = p;
+    void *args[] = {&q, &fq, &two, &pq};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_frames_kernel<1, Phi4EnsPCorrArgs>
+                     : sh.K == 2 ? (const void *)&phi4_ens_frames_kernel<2, Phi4EnsPCorrArgs>
+                     : sh.K == 4 ? (const void *)&phi4_ens_frames_kernel<4, Phi4EnsPCorrArgs>
+                                 : (const void *)&phi4_ens_frames_kernel<8, Phi4EnsPCorrArgs>;
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+}
+
+hipError_t phi4_ens_pslices_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs &p, int first, int count, double *AB,
+                                   double *g, hipStream_t s) {
+    if (!ens_shape_ok(a) || first < 0 || count < 1 || AB == nullptr || g == nullptr || !ens_pcorr_ok(p, false))
+        return hipErrorInvalidValue;
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    if (!sh.pc_ok) return hipErrorInvalidValue;
+    const int bytes = sh.pc_sl_lds_bytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsPCorrArgs pq = p;
+    void *args[] = {&q, &pq, &first, &AB, &g};
+    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_pslices_kernel<1>
+                     : sh.K == 2 ? (const void *)&phi4_ens_pslices_kernel<2>
+                     : sh.K == 4 ? (const void *)&phi4_ens_pslices_kernel<4>
+                                 : (const void *)&phi4_ens_pslices_kernel<8>;
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)count), dim3((unsigned)sh.T), args, (size_t)bytes, s);
 }
 
 hipError_t phi4_ens_step_launch(const Phi4EnsArgs &a, int nrep, hipStream_t s) {

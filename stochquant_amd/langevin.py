@@ -522,7 +522,9 @@ class Phi4Ensemble:
     steps (`step`) or whole frames (`run_frames`): `loops` steps, the stability
     rule, the rollback and, with `adapt_dtau`, the Δτ controller, decided per
     replica inside the kernel, one launch per call, as `Phi4Lattice.run_frames`
-    decides them for one lattice.
+    decides them for one lattice.  Both can measure, in flight, the time-slice
+    correlator over z at zero momentum (`correlate`) and at up to eight spatial
+    momenta set with `set_momenta` (`momenta`).
 
     dtau, m2, lam and C are scalars or length-R sequences; seeds defaults to
     seed + r."""
@@ -660,7 +662,7 @@ class Phi4Ensemble:
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64), (self.R,)))
         _lib.call("sq_phi4_ens_set_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
 
-    def step(self, n=1, every=0, correlate=False):
+    def step(self, n=1, every=0, correlate=False, momenta=False):
         """n steps of every replica in one launch.  every = k > 0: returns the
         (n // k, R, 4) array of S1 = Σφ, S2 = Σφ², S4 = Σφ⁴ and NN = Σ over
         sites and the three forward links of φ(x) φ(x + μ), recorded after each
@@ -668,33 +670,41 @@ class Phi4Ensemble:
         every >= 1): the kernel also adds one time-slice correlator measurement
         after each k-th step to the replicas' accumulators (`corr_sums`,
         `correlator`); fields, counters, flags and the return value are those of
-        the same call without it."""
+        the same call without it.  `momenta` (needs every >= 1 and
+        `set_momenta`): likewise one measurement of the momentum-projected
+        correlators (`pcorr_sums`, `pcorrelator`)."""
         n, every = int(n), int(every)
-        fn = "sq_phi4_ens_step"
-        if correlate:
+        fn, extra = "sq_phi4_ens_step", ()
+        if correlate or momenta:
             if every < 1:
-                raise ValueError("correlate=True needs every >= 1")
+                raise ValueError("correlate=True and momenta=True need every >= 1")
             fn = "sq_phi4_ens_step_corr"
+        if momenta:
+            fn, extra = "sq_phi4_ens_step_pcorr", (1 if correlate else 0,)
         if every <= 0:
             _lib.call(fn, self._h, n, 0, None)
             return None
         ser = np.zeros((max(n, 0) // every, self.R, 4))
-        _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None)
+        _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
         return ser
 
-    def run_frames(self, n, measure=False, correlate=False):
+    def run_frames(self, n, measure=False, correlate=False, momenta=False):
         """n frames of every replica in one launch: (stable (n, R) bool, dtau
         (n, R) after each frame), and with `measure` the (n, R, 4) sums S1, S2,
         S4, NN of each replica's field after the frame's verdict (the frame's
         start field again after a rollback).  `correlate`: one correlator
         measurement of the adopted field after every stable frame of a replica
-        (a rolled-back frame measures nothing); the return values are unchanged."""
+        (a rolled-back frame measures nothing); the return values are unchanged.
+        `momenta`: likewise one measurement of the momentum-projected correlators."""
         n = int(n)
         st = np.zeros((max(n, 0), self.R), dtype=np.int32)
         dt = np.zeros((max(n, 0), self.R))
         ser = np.zeros((max(n, 0), self.R, 4)) if measure else None
-        _lib.call("sq_phi4_ens_run_frames_corr" if correlate else "sq_phi4_ens_run_frames", self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
-                  None if ser is None else _dptr(ser))
+        fn, extra = ("sq_phi4_ens_run_frames_corr" if correlate else "sq_phi4_ens_run_frames"), ()
+        if momenta:
+            fn, extra = "sq_phi4_ens_run_frames_pcorr", (1 if correlate else 0,)
+        _lib.call(fn, self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
+                  None if ser is None else _dptr(ser), *extra)
         if n > 0:
             self._frames_run = True
         return (st != 0, dt) if ser is None else (st != 0, dt, ser)
@@ -784,6 +794,79 @@ class Phi4Ensemble:
         dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
         out = (ctypes.c_int * 6)()
         _lib.call("sq_phi4_ens_corr_shape_info", dims, out)
+        return dict(zip(("images", "lds_bytes", "frames_images", "frames_lds_bytes", "slices_lds_bytes", "nt"),
+                        (int(v) for v in out)))
+
+    @staticmethod
+    def momentum_table(L, n):
+        """(c, s): the twiddle table of momentum index n on an axis of L sites,
+        c[k] = cos(2π j / L), s[k] = sin(2π j / L), j = (n k) mod L, exact at the
+        quarter turns (sq_phi4_ens_momentum_table; no device needed).  The
+        kernels use these values."""
+        c, s = np.zeros(max(int(L), 0)), np.zeros(max(int(L), 0))
+        _lib.call("sq_phi4_ens_momentum_table", int(L), int(n), _dptr(c), _dptr(s))
+        return c, s
+
+    def set_momenta(self, pairs):
+        """The spatial momenta (nx, ny), p = (2π nx / Lx, 2π ny / Ly), measured
+        by step(momenta=True) and run_frames(momenta=True): at most 8, duplicates
+        allowed.  Zeroes the momentum accumulators of every replica."""
+        a = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2))
+        _lib.call("sq_phi4_ens_set_momenta", self._h, a.shape[0], a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    @property
+    def momenta(self):
+        """The momenta set: a list of (nx, ny)."""
+        M = ctypes.c_int(0)
+        a = np.zeros((_lib.SQ_PHI4_ENS_MAX_MOMENTA, 2), dtype=np.int32)
+        _lib.call("sq_phi4_ens_get_momenta", self._h, ctypes.byref(M), a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return [(int(x), int(y)) for x, y in a[:M.value]]
+
+    def pcorr_sums(self, first=0, count=None):
+        """The raw momentum accumulators of replicas first .. first + count: (G
+        (count, M, nt) = Σ over measurements of g_m(t) = Σ_z [A(z) A(z + t) +
+        B(z) B(z + t)], nmeas (count,) int64), A + iB the slice's projection on
+        momentum m; see include/stochquant.h for the arithmetic."""
+        k, M = self._count(first, count), len(self.momenta)
+        G = np.zeros((max(k, 0), M, self.nt))
+        nm = np.zeros(max(k, 0), dtype=np.int64)
+        _lib.call("sq_phi4_ens_pcorr_sums", self._h, int(first), k, _dptr(G),
+                  nm.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return G, nm
+
+    def pcorr_reset(self, first=0, count=None):
+        """Zero the momentum accumulators of replicas first .. first + count."""
+        _lib.call("sq_phi4_ens_pcorr_reset", self._h, int(first), self._count(first, count))
+
+    def pslices(self, first=0, count=None):
+        """One momentum measurement of the current fields, accumulating nothing:
+        (AB (count, M, Lz, 2) projections A and B, g (count, M, nt))."""
+        k, M = self._count(first, count), len(self.momenta)
+        AB = np.zeros((max(k, 0), M, self.shape[2], 2))
+        g = np.zeros((max(k, 0), M, self.nt))
+        _lib.call("sq_phi4_ens_pslices", self._h, int(first), k, _dptr(AB), _dptr(g))
+        return AB, g
+
+    def pcorrelator(self, n=None):
+        """(mean (M, n), err (M, n), used): per momentum the replica mean and
+        standard error of c_r(m, t) = Gp_r[m][t] / (nmeas_p,r V), as `correlator`
+        computes them with connected=False.  Raises StochQuantError (SQ_E_STATE)
+        when no replica has a momentum measurement."""
+        n, M = (self.nt if n is None else int(n)), len(self.momenta)
+        mean, err = np.zeros((M, max(n, 0))), np.zeros((M, max(n, 0)))
+        used = ctypes.c_int(0)
+        _lib.call("sq_phi4_ens_pcorrelator", self._h, _dptr(mean), _dptr(err), n, ctypes.byref(used))
+        return mean, err, used.value
+
+    @staticmethod
+    def pcorr_shape_info(shape):
+        """The momentum launches' LDS layout for a lattice of `shape`
+        (sq_phi4_ens_pcorr_shape_info; no device needed): the keys of
+        `corr_shape_info`, "slices_lds_bytes" being the pslices launch's.  Raises
+        StochQuantError (SQ_E_ARG) for a shape that cannot hold momenta."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 6)()
+        _lib.call("sq_phi4_ens_pcorr_shape_info", dims, out)
         return dict(zip(("images", "lds_bytes", "frames_images", "frames_lds_bytes", "slices_lds_bytes", "nt"),
                         (int(v) for v in out)))
 
