@@ -569,6 +569,36 @@ int sq_phi4_ens_pslices(sq_phi4_ens *e, int first, int count, double *AB /*[coun
 int sq_phi4_ens_pcorrelator(sq_phi4_ens *e, double *mean /*[M][n]*/, double *err, int n, int *used);
 int sq_phi4_ens_pcorr_shape_info(const int dims[3], int out[6]);
 
+/* A second-order integrator for the ensemble's raw steps: the stochastic Heun
+ * scheme with additive noise.  With E_s the update sq_phi4_ens_step applies at
+ * step counter s (the replica's coefficients and key, the normals of s, the
+ * guard; the noise-off form where C = 0), one Heun step of a replica is
+ *   p    = E_s(phi)
+ *   e    = E_s(p)          the same counter, hence the same normals
+ *   phi' = guard(0.5f * (phi + e))   one fp32 add, one fp32 multiply per site
+ * with the guard of the update itself (NaN -> +clamp, else clipped to [-clamp,
+ * clamp]); the counter advances by ONE.  This is phi + dtau/2 (F(phi) + F(p)) +
+ * sigma xi: its stationary distribution is off at O(dtau^2) where the Euler
+ * step's is off at O(dtau).  A replica's guard flag is set when max |p|, max
+ * |e| or max |phi'| reached the clamp.  Replica r is bit for bit that
+ * composition of sq_step calls on the single context of the same parameters
+ * and seed with the counter set back between them; the bits do not depend on
+ * nrep, the replica's index or the work-group shape, Heun and Euler calls may
+ * alternate on one handle, and calls split in any way give the same bits.
+ *
+ * sq_phi4_ens_step_heun: nsteps Heun steps of every replica in one launch.
+ * every, series: as sq_phi4_ens_step, counting Heun steps.  measure: bit 0
+ * adds what sq_phi4_ens_step_corr adds, bit 1 what sq_phi4_ens_step_pcorr
+ * adds (M = 0: SQ_E_STATE), both bits what its correlate != 0 adds; with
+ * either bit every >= 1, else SQ_E_ARG; other bits: SQ_E_ARG.  nsteps = 0 does
+ * nothing.  sq_phi4_ens_perf counts one step (and `sites` site updates) per
+ * Heun step, although each does the work of two.  Frames
+ * (sq_phi4_ens_run_frames*) always take Euler steps.  SQ_SCHEME_*: the names
+ * of the two integrators (Phi4Ensemble.step's "euler" / "heun"). */
+#define SQ_SCHEME_EULER 0
+#define SQ_SCHEME_HEUN 1
+int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series, int measure);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

@@ -201,6 +201,7 @@ SIGNATURES = {
     "sq_phi4_ens_set_momenta": (ctypes.c_int, [_P, ctypes.c_int, _I]),
     "sq_phi4_ens_get_momenta": (ctypes.c_int, [_P, _I, _I]),
     "sq_phi4_ens_step_pcorr": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int]),
+    "sq_phi4_ens_step_heun": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int]),
     "sq_phi4_ens_run_frames_pcorr": (ctypes.c_int, [_P, ctypes.c_int, _I, _D, _D, ctypes.c_int]),
     "sq_phi4_ens_pcorr_sums": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ens_pcorr_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),

@@ -187,8 +187,10 @@ sq::Phi4EnsPCorrArgs ens_pcorr_args(const sq_phi4_ens *e, bool corr) {
 }
 
 // sq_phi4_ens_step (corr = false), sq_phi4_ens_step_corr (corr = true) and sq_phi4_ens_step_pcorr (pcorr = true,
-// corr its `correlate`); with either measurement every >= 1, checked by the caller
-int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr, bool pcorr = false) {
+// corr its `correlate`); with either measurement every >= 1, checked by the caller.  heun: the same call with
+// the Heun kernel (sq_phi4_ens_step_heun); one Heun step counts as one step everywhere on the host.
+int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr, bool pcorr = false,
+             bool heun = false) {
     if (nsteps == 0) return SQ_OK;
     DeviceGuard g(e->dev);
     int rc = ens_sync_recs(e);
@@ -209,7 +211,11 @@ int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, bool corr, b
     a.nsteps = nsteps;
     a.every = (nd || corr || pcorr) ? every : 0;
     a.series = nd ? e->series : nullptr;
-    if (pcorr) SQ_HIP(sq::phi4_ens_step_pcorr_launch(a, ens_pcorr_args(e, corr), e->R, e->stream));
+    if (heun) {
+        const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+        const sq::Phi4EnsPCorrArgs p = pcorr ? ens_pcorr_args(e, corr) : sq::Phi4EnsPCorrArgs{};
+        SQ_HIP(sq::phi4_ens_heun_launch(a, (corr && !pcorr) ? &c : nullptr, pcorr ? &p : nullptr, e->R, e->stream));
+    } else if (pcorr) SQ_HIP(sq::phi4_ens_step_pcorr_launch(a, ens_pcorr_args(e, corr), e->R, e->stream));
     else if (corr) SQ_HIP(sq::phi4_ens_step_corr_launch(a, ens_corr_args(e), e->R, e->stream));
     else SQ_HIP(sq::phi4_ens_step_launch(a, e->R, e->stream));
     e->launches++;
@@ -663,6 +669,16 @@ int sq_phi4_ens_step_pcorr(sq_phi4_ens *e, int nsteps, int every, double *series
     if (every < 1) return fail(SQ_E_ARG, "a momentum measurement needs every >= 1");
     if (e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
     return ens_step(e, nsteps, every, series, correlate != 0, true);
+}
+
+int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series, int measure) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (measure & ~3) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) and bit 1 (momenta) only");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator or momentum measurement needs every >= 1" : "every must be >= 0");
+    if ((measure & 2) && e->pM == 0) return fail(SQ_E_STATE, "no momenta set (sq_phi4_ens_set_momenta)");
+    return ens_step(e, nsteps, every, series, (measure & 1) != 0, (measure & 2) != 0, true);
 }
 
 int sq_phi4_ens_run_frames_pcorr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series,

@@ -140,6 +140,13 @@ hipError_t phi4_ens_frames_pcorr_launch(const Phi4EnsArgs &a, const Phi4EnsFrame
 // AB[r][M][Lz][2] projections, g[r][M][nt] (device memory, both non-null); p.Gp, p.nmeas_p, p.corr are not used.
 hipError_t phi4_ens_pslices_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs &p, int first, int count, double *AB,
                                    double *g, hipStream_t s);
+// nsteps stochastic Heun steps of every replica in one launch (phi4_ens_heun_kernel): per step
+// phi' = guard(0.5 (phi + E(E(phi)))), E the step launch's update, both applications with the normals of the
+// step's counter, which advances by one.  c, p nullable, at most one of them: the measurements of
+// phi4_ens_step_corr_launch / phi4_ens_step_pcorr_launch after each every-th Heun step.  The work-group shape,
+// the LDS layout and the argument rules are those of the three step launches.
+hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, const Phi4EnsPCorrArgs *p, int nrep,
+                                hipStream_t s);
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

@@ -39,6 +39,10 @@
 // stored field.  The momentum instances add ens_pcorr, the same correlator
 // projected on spatial momenta (p_x, p_y); phi4_ens_pslices_kernel is that
 // routine on the stored field.
+//
+// phi4_ens_heun_kernel is the step kernel with the second-order stochastic
+// Heun step in place of the Euler one: phi' = guard(0.5 (phi + E(E(phi)))), E
+// the update above applied twice with the normals of one counter (ens_heun).
 #define SQ_PHI4_KERNELS_ONLY
 #include <type_traits>
 
@@ -455,6 +459,210 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_kernel(const P
     for (int j = 0; j < K; ++j)
         if (fl[j] & kEnsValid) gf[(int)threadIdx.x + j * T] = c[j];
     // some site was clamped (NaN -> +clamp) iff the running max after the guard reached the clamp
+    if (am >= E.clampv) E.flags[r] = 1;
+}
+
+// The guard of site_update on a value formed outside it: NaN -> +clamp, else clipped to [-clamp, clamp].
+__device__ __forceinline__ float ens_guard(float v, float cl) { return fmaxf(fminf(v, cl), -cl); }
+
+// The K flag words of a lane, four to a register (each has seven bits): the Heun kernel's K = 8 instances
+// have no register to spare, and a shift and a mask per quad and loop buy six.
+template <int K>
+struct EnsFlagsPk {
+    uint32_t w[(K + 3) / 4];
+    __device__ __forceinline__ void pack(const uint32_t (&fl)[K]) {
+#pragma unroll
+        for (int i = 0; i < (K + 3) / 4; ++i) w[i] = 0u;
+#pragma unroll
+        for (int j = 0; j < K; ++j) w[j >> 2] |= fl[j] << (8 * (j & 3));
+    }
+    __device__ __forceinline__ uint32_t get(int j) const {
+        uint32_t v = w[j >> 2];
+        asm volatile("" : "+v"(v));  // opaque per use: the unpacked words are not hoisted and kept
+        return (v >> (8 * (j & 3))) & 0xffu;
+    }
+};
+
+// One stochastic Heun step of the lane's K quads: with E the
+// update of ens_step at counter s, c <- guard(0.5 (c + E(E(c)))), both
+// applications with the normals of s.  The lane keeps phi in c throughout;
+// p = E(phi) lives in an image only, and stage 2 reads the lane's own p quad
+// back beside its six neighbour reads.  On return cur holds phi' behind a
+// block barrier, as after a step of phi4_ens_step_kernel.
+//
+// TWO (two images): stage 1 reads cur (phi) and writes p to oth, barrier,
+// stage 2 reads oth and writes phi' to cur, barrier.  cur is read by stage 1
+// and written by stage 2 only, oth the other way round, and a barrier stands
+// between every stage and the next: two barriers per step.
+// One image: stage 1 forms p into c from the image, barrier (every phi
+// neighbour read is done), the lane exchanges its own quads -- phi back from
+// the image into c, p into the image: no lane touches another lane's quad --
+// barrier, stage 2 forms phi' into c from the image of p, barrier (every p
+// read is done), phi' to the image, barrier: four barriers per step.
+//
+// KEEP: the normals of stage 1 stay in registers for stage 2 (4 K VGPRs);
+// otherwise stage 2 evaluates tb_noise again: the same counter and key, so
+// the same bits.  am takes max |p|, max |e| and max |phi'|, each after its guard.
+template <int K, bool NZ, bool TWO>
+__device__ __forceinline__ void ens_heun(const Phi4StepArgs &A, const EnsGeo &g, float4 (&c)[K],
+                                         const EnsFlagsPk<K> &fl, float *cur, float *oth, uint32_t slo, uint32_t shi,
+                                         float &am) {
+    constexpr bool KEEP = NZ && K <= 4;
+    const int T = blockDim.x;
+    f32x4n xk[KEEP ? K : 1] = {};
+    {
+        const float *img = cur;
+        const float4 *img4 = reinterpret_cast<const float4 *>(img);
+        float4 *oth4 = reinterpret_cast<float4 *>(oth);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            uint32_t f = fl.get(j);
+            int q = (int)threadIdx.x + j * T;
+            asm volatile("" : "+v"(f), "+v"(q));  // as ens_step
+            if (f & kEnsValid) {
+                const EnsNbr n = ens_nbr(g, q, f);
+                const float4 up = img4[n.up], dn = img4[n.dn], zm = img4[n.zm], zp = img4[n.zp];
+                const float lft = img[n.lf], rgt = img[n.rg];
+                const f32x4n xi = tb_noise<NZ>(A, 0u, (uint32_t)q, slo, shi);
+                if constexpr (KEEP) xk[j] = xi;
+                float mp;
+                const float4 p = site_update4<NZ>(c[j], lft, rgt, up, dn, zm, zp, xi, A, false, f32x2{A.m2, A.m2}, &mp);
+                am = fmaxf(am, mp);
+                if constexpr (TWO) oth4[q] = p;
+                else c[j] = p;
+            }
+        }
+    }
+    if constexpr (!TWO) {
+        __syncthreads();  // every wave has read phi
+        float4 *cur4 = reinterpret_cast<float4 *>(cur);
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            uint32_t f = fl.get(j);
+            int q = (int)threadIdx.x + j * T;
+            asm volatile("" : "+v"(f), "+v"(q));
+            if (f & kEnsValid) {
+                const float4 phi = cur4[q];
+                cur4[q] = c[j];
+                c[j] = phi;
+            }
+        }
+    }
+    __syncthreads();  // p is in its image
+    {
+        const float *img = TWO ? oth : cur;
+        const float4 *img4 = reinterpret_cast<const float4 *>(img);
+        float4 *cur4 = reinterpret_cast<float4 *>(cur);
+        const float cl = A.clampv;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            uint32_t f = fl.get(j);
+            int q = (int)threadIdx.x + j * T;
+            asm volatile("" : "+v"(f), "+v"(q));
+            if (f & kEnsValid) {
+                const EnsNbr n = ens_nbr(g, q, f);
+                const float4 p = img4[q];
+                const float4 up = img4[n.up], dn = img4[n.dn], zm = img4[n.zm], zp = img4[n.zp];
+                const float lft = img[n.lf], rgt = img[n.rg];
+                f32x4n xi;
+                if constexpr (KEEP) xi = xk[j];
+                else xi = tb_noise<NZ>(A, 0u, (uint32_t)q, slo, shi);
+                float mp;
+                const float4 e = site_update4<NZ>(p, lft, rgt, up, dn, zm, zp, xi, A, false, f32x2{A.m2, A.m2}, &mp);
+                float4 o;
+                o.x = ens_guard(__fmul_rn(0.5f, __fadd_rn(c[j].x, e.x)), cl);
+                o.y = ens_guard(__fmul_rn(0.5f, __fadd_rn(c[j].y, e.y)), cl);
+                o.z = ens_guard(__fmul_rn(0.5f, __fadd_rn(c[j].z, e.z)), cl);
+                o.w = ens_guard(__fmul_rn(0.5f, __fadd_rn(c[j].w, e.w)), cl);
+                c[j] = o;
+                // after the guard: never NaN
+                am = fmaxf(am, fmaxf(mp, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)))));
+                if constexpr (TWO) cur4[q] = o;
+            }
+        }
+        if constexpr (!TWO) {
+            __syncthreads();  // every wave has read p
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (fl.get(j) & kEnsValid) cur4[(int)threadIdx.x + j * T] = c[j];
+        }
+    }
+    __syncthreads();  // phi' is in cur
+}
+
+// phi4_ens_step_kernel with ens_heun as its step (sq_phi4_ens_step_heun): the
+// same arguments, LDS layout and work-group shape, the counter advancing by one
+// per Heun step; cur is img0 for the whole call.  The measurement code behind
+// the step is that kernel's, `left` / `every` counting Heun steps.
+template <int K, typename... CA>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_heun_kernel(const Phi4EnsArgs E, const int two,
+                                                                          const CA... ca) {
+    constexpr bool PC = kEnsPCorr<CA...>;
+    constexpr bool CORR = sizeof...(CA) != 0;  // either kind of measurement
+    const int r = blockIdx.x;
+    const EnsGeo g = ens_geo(E);
+    const Phi4EnsRec rc = E.rec[r];
+    Phi4StepArgs A{};
+    A.h = rc.h;
+    A.m2 = rc.m2;
+    A.lam6 = rc.lam6;
+    A.sig = rc.sig;
+    A.sigq = rc.sigq;
+    A.clampv = E.clampv;
+    A.k0 = rc.k0;
+    A.k1 = rc.k1;
+    const bool nz = rc.sig != 0.0f;  // phi4_step_launch's choice of instance
+    float *cur = reinterpret_cast<float *>(ens_smem);
+    float *oth = two ? cur + 4 * g.Q : cur;
+    double *scr = reinterpret_cast<double *>(ens_smem + (size_t)(two ? 2 : 1) * 16 * (size_t)g.Q);
+    float4 c[K];
+    EnsFlagsPk<K> fl;
+    {
+        uint32_t f[K];
+        ens_load<K>(E, g, r, c, f, cur);
+        fl.pack(f);
+    }
+    const int T = blockDim.x;
+    float am = 0.f;
+    const unsigned long long s0 = rc.step + E.adv;
+    int left = E.every;  // steps until the next measurement
+    int rec = 0;
+    for (int t = 0; t < E.nsteps; ++t) {
+        const unsigned long long s = s0 + (unsigned long long)t;
+        const uint32_t slo = (uint32_t)s, shi = (uint32_t)(s >> 32);
+        if (two) {
+            if (nz) ens_heun<K, true, true>(A, g, c, fl, cur, oth, slo, shi, am);
+            else ens_heun<K, false, true>(A, g, c, fl, cur, oth, slo, shi, am);
+        } else {
+            if (nz) ens_heun<K, true, false>(A, g, c, fl, cur, oth, slo, shi, am);
+            else ens_heun<K, false, false>(A, g, c, fl, cur, oth, slo, shi, am);
+        }
+        if ((CORR || E.series != nullptr) && --left == 0) {
+            left = E.every;
+            if (!CORR || E.series != nullptr) {
+                double sm[4];
+                float mx;
+                uint32_t f[K];
+#pragma unroll
+                for (int j = 0; j < K; ++j) f[j] = fl.get(j);
+                ens_sums<K>(g, c, f, cur, sm, mx);
+                ens_fold(sm, mx, scr, E.series + 4 * ((size_t)rec * gridDim.x + (size_t)r), false);
+                ++rec;
+            }
+            if constexpr (PC) {
+                ens_pcorr_measure(g, E, r, cur, scr + kPhi4EnsScratchBytes / 8, ens_pcorr_args(ca...));
+            } else if constexpr (CORR) {
+                const Phi4EnsCorrArgs C = ens_corr_args(ca...);
+                ens_corr<true>(g, E.Lz, cur, scr + kPhi4EnsScratchBytes / 8, C.G + (size_t)r * (size_t)(E.Lz / 2 + 1),
+                               C.S1 + r, C.nmeas + r, nullptr);
+            }
+        }
+    }
+    float4 *gf = reinterpret_cast<float4 *>(E.field + (size_t)r * (size_t)(4 * g.Q));
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        if (fl.get(j) & kEnsValid) gf[(int)threadIdx.x + j * T] = c[j];
+    // a stage's guarded maximum or the final guard reached the clamp
     if (am >= E.clampv) E.flags[r] = 1;
 }
 
@@ -929,6 +1137,41 @@ hipError_t phi4_ens_step_corr_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs
     hipError_t e = ens_lds_attr(fn, sh.co_lds_bytes);
     if (e != hipSuccess) return e;
     return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.co_lds_bytes, s);
+}
+
+namespace {
+template <typename... CA>
+const void *ens_heun_fn(int K) {
+    return K == 1   ? (const void *)&phi4_ens_heun_kernel<1, CA...>
+           : K == 2 ? (const void *)&phi4_ens_heun_kernel<2, CA...>
+           : K == 4 ? (const void *)&phi4_ens_heun_kernel<4, CA...>
+                    : (const void *)&phi4_ens_heun_kernel<8, CA...>;
+}
+}  // namespace
+
+hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, const Phi4EnsPCorrArgs *p, int nrep,
+                                hipStream_t s) {
+    const bool meas = c != nullptr || p != nullptr;
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < (meas ? 1 : 0) ||
+        (a.series != nullptr && a.every < 1) || (c != nullptr && p != nullptr))
+        return hipErrorInvalidValue;
+    if (c != nullptr && (c->G == nullptr || c->S1 == nullptr || c->nmeas == nullptr)) return hipErrorInvalidValue;
+    if (p != nullptr && !ens_pcorr_ok(*p, true)) return hipErrorInvalidValue;
+    // the step launches' layouts, each by its own rule
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, meas ? a.Lz : 0);
+    if (p != nullptr && !sh.pc_ok) return hipErrorInvalidValue;
+    int two = (p ? sh.pc_two : c ? sh.co_two : sh.two) ? 1 : 0;
+    const int bytes = p ? sh.pc_lds_bytes : c ? sh.co_lds_bytes : sh.lds_bytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsCorrArgs cq = c ? *c : Phi4EnsCorrArgs{};
+    Phi4EnsPCorrArgs pq = p ? *p : Phi4EnsPCorrArgs{};
+    void *args[] = {&q, &two, p ? (void *)&pq : (void *)&cq};  // the plain instances take the first two
+    const void *fn = p   ? ens_heun_fn<Phi4EnsPCorrArgs>(sh.K)
+                     : c ? ens_heun_fn<Phi4EnsCorrArgs>(sh.K)
+                         : ens_heun_fn<>(sh.K);
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
 }
 
 hipError_t phi4_ens_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, int nrep, hipStream_t s) {

@@ -662,7 +662,7 @@ class Phi4Ensemble:
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64), (self.R,)))
         _lib.call("sq_phi4_ens_set_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
 
-    def step(self, n=1, every=0, correlate=False, momenta=False):
+    def step(self, n=1, every=0, correlate=False, momenta=False, scheme="euler"):
         """n steps of every replica in one launch.  every = k > 0: returns the
         (n // k, R, 4) array of S1 = Σφ, S2 = Σφ², S4 = Σφ⁴ and NN = Σ over
         sites and the three forward links of φ(x) φ(x + μ), recorded after each
@@ -672,7 +672,16 @@ class Phi4Ensemble:
         `correlator`); fields, counters, flags and the return value are those of
         the same call without it.  `momenta` (needs every >= 1 and
         `set_momenta`): likewise one measurement of the momentum-projected
-        correlators (`pcorr_sums`, `pcorrelator`)."""
+        correlators (`pcorr_sums`, `pcorrelator`).
+
+        scheme: "euler" (the default, first order in Δτ) or "heun", the
+        second-order stochastic Heun step (sq_phi4_ens_step_heun): with E the
+        Euler update at the step's counter, φ' = guard(0.5 (φ + E(E(φ)))), both
+        applications with the same noise; the counter advances by one per Heun
+        step, and `every`, `correlate` and `momenta` count and measure Heun
+        steps.  Calls of either scheme may alternate."""
+        if scheme not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n, every = int(n), int(every)
         fn, extra = "sq_phi4_ens_step", ()
         if correlate or momenta:
@@ -681,8 +690,10 @@ class Phi4Ensemble:
             fn = "sq_phi4_ens_step_corr"
         if momenta:
             fn, extra = "sq_phi4_ens_step_pcorr", (1 if correlate else 0,)
+        if scheme == "heun":
+            fn, extra = "sq_phi4_ens_step_heun", ((1 if correlate else 0) | (2 if momenta else 0),)
         if every <= 0:
-            _lib.call(fn, self._h, n, 0, None)
+            _lib.call(fn, self._h, n, 0, None, *extra)
             return None
         ser = np.zeros((max(n, 0) // every, self.R, 4))
         _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
