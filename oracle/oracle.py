@@ -88,6 +88,8 @@ def lib():
         L.orc_phi4_stab_rule.argtypes = [_F, _F, _F, _F, _F, ctypes.c_int]
         L.orc_phi4_step_range.argtypes = [ctypes.POINTER(Phi4), _F, _F, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+        L.orc_phi4_heun_step.restype = ctypes.c_int
+        L.orc_phi4_heun_step.argtypes = [ctypes.POINTER(Phi4), _F, _F, ctypes.c_uint64, _F]
         L.orc_phi4_sigma.restype = ctypes.c_float
         L.orc_phi4_sigma.argtypes = [ctypes.c_float, ctypes.c_double]
         _lib = L
@@ -232,6 +234,19 @@ def phi4_step(p, phi, step, nthreads=0):
     out = np.empty_like(a)
     lib().orc_phi4_step(ctypes.byref(p), a.ctypes.data_as(_F), out.ctypes.data_as(_F), step, nthreads)
     return out
+
+
+def phi4_heun_step(p, phi, step):
+    """One stochastic Heun step at counter `step` (orc_phi4_heun_step): returns
+    (phi', (max|p|, max|e|, max|phi'|)), the maxima as float32, each taken
+    after its stage's guard."""
+    a = np.ascontiguousarray(phi, dtype=np.float32)
+    out = np.empty_like(a)
+    mx = np.zeros(3, dtype=np.float32)
+    if lib().orc_phi4_heun_step(ctypes.byref(p), a.ctypes.data_as(_F), out.ctypes.data_as(_F), step,
+                                mx.ctypes.data_as(_F)) != 0:
+        raise MemoryError("orc_phi4_heun_step")
+    return out, (mx[0], mx[1], mx[2])
 
 
 def phi4_step_slab(p, padded, z0, step):

@@ -131,6 +131,55 @@ void orc_phi4_step_stab(const orc_phi4 *p, const float *in, float *out, uint64_t
     rec[2] = amax;
 }
 
+/* max |v| over n values that have passed the guard (never NaN). */
+static float max_abs(const float *v, size_t n)
+{
+    float m = 0.f;
+    for (size_t i = 0; i < n; ++i)
+        if (fabsf(v[i]) > m) m = fabsf(v[i]);
+    return m;
+}
+
+/* The stochastic Heun step of include/stochquant.h, from its definition: with
+ * E the update of orc_phi4_step at counter `step`, p = E(in), e = E(p) (the
+ * same counter, hence the same normals), out = guard(0.5f * (in + e)): one
+ * fp32 add, one fp32 multiply (-ffp-contract=off keeps them apart), then the
+ * update's own guard.  maxima = {max |p|, max |e|, max |out|}, each taken
+ * after its guard.  Single-threaded.  Returns -1 (out untouched) when the two
+ * work lattices cannot be allocated. */
+int orc_phi4_heun_step(const orc_phi4 *p, const float *in, float *out, uint64_t step, float maxima[3])
+{
+    const int Lz = p->Lz;
+    const size_t plane = (size_t)p->Lx * p->Ly, n = plane * (size_t)Lz;
+    const float mx = p->clampv;
+    float *st = (float *)malloc(2 * n * sizeof(float));
+    if (!st) return -1;
+    float *s1 = st, *s2 = st + n;
+    const float *src = in;
+    float *dst = s1;
+    for (int stage = 0; stage < 2; ++stage) {
+        for (int z = 0; z < Lz; ++z) {
+            const int zm = (z + Lz - 1) % Lz, zp = (z + 1) % Lz;
+            phi4_plane(p, src + (size_t)z * plane, src + (size_t)zm * plane, src + (size_t)zp * plane,
+                       dst + (size_t)z * plane, (uint64_t)z, step, NULL, NULL);
+        }
+        src = s1;
+        dst = s2;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const float sum = in[i] + s2[i];
+        const float v = 0.5f * sum;
+        out[i] = isnan(v) ? mx : (v > mx ? mx : (v < -mx ? -mx : v));
+    }
+    if (maxima) {
+        maxima[0] = max_abs(s1, n);
+        maxima[1] = max_abs(s2, n);
+        maxima[2] = max_abs(out, n);
+    }
+    free(st);
+    return 0;
+}
+
 int orc_phi4_stab_rule(float *T, float *V, const float *M, const float *D, const float *A, int n)
 {
     for (int j = 0; j < n; ++j) {

@@ -129,6 +129,15 @@ void orc_phi4_step_range(const orc_phi4 *p, const float *in, float *out, int nz,
  * attaining M of |phi' - phi - sigma xi| (fp32, fmaf(-sigma, xi, phi' - phi)),
  * A = max |phi'|}.  Single-threaded. */
 void orc_phi4_step_stab(const orc_phi4 *p, const float *in, float *out, uint64_t step, float rec[3]);
+/* One stochastic Heun step (include/stochquant.h, sq_phi4_ens_step_heun),
+ * written from its definition: p = E(in), e = E(p) with E = orc_phi4_step at
+ * the one counter `step`, out = guard(0.5f * (in + e)) (one fp32 add, one fp32
+ * multiply, NaN -> +clamp, else clipped).  maxima (nullable) = {max |p|,
+ * max |e|, max |out|}, each after its guard: the replica's guard flag is
+ * any(maxima >= clamp).  In device-transcendental mode the normals are those
+ * of orc_phi4_step.  Single-threaded; `out` may be `in`.  Returns 0, or -1
+ * when the work lattices cannot be allocated. */
+int orc_phi4_heun_step(const orc_phi4 *p, const float *in, float *out, uint64_t step, float maxima[3]);
 /* The frame rule over n step records: returns the first step with M > T and
  * D > V (-1: none); T <- M_j and V <- max(V, A_j) through that step. */
 int orc_phi4_stab_rule(float *T, float *V, const float *M, const float *D, const float *A, int n);

@@ -8,7 +8,8 @@
   * phi^4 ensemble: legal shapes spread over the four K classes of its
     work-group, two replicas with different parameters; C = 0 and C = 1 (with
     the device's Box-Muller factors) bit-identical, series rows within the
-    fsum bound.
+    fsum bound.  The same for its Heun step against the oracle's Heun entry,
+    from drawn per-replica start counters up to 2^40.
   * QM1D serial order: random N, loops, Δτ and potID 0 frames with injected
     reference noise, bit-identical frame by frame.
 """
@@ -100,6 +101,48 @@ def test_phi4_ens_random_shapes(gpu, oracle_mod, bm_tables, shape, steps, every,
                     err = np.abs(ser[(s + 1) // every - 1, r] - exact)
                     assert np.all(err <= bound), (shape, info, r, s, err, bound)
             assert np.array_equal(got[r], ref[r]), (shape, info, r, C, np.max(np.abs(got[r] - ref[r])))
+
+
+@settings(max_examples=30, deadline=None, derandomize=True,
+          suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
+@given(shape=_ens_shapes(), steps=st.integers(1, 3), every=st.integers(0, 2), C=st.sampled_from([0.0, 1.0]),
+       seed=st.integers(0, 2 ** 40), dtau=st.sampled_from([(0.005, 0.02), (0.02, 0.05), (0.05, 0.005)]),
+       m2=st.sampled_from([(0.5, -0.5), (1.0, 0.25)]), lam=st.sampled_from([(1.0, 2.0), (4.0, 0.5)]),
+       step0=st.tuples(st.integers(0, 2 ** 40), st.integers(0, 2 ** 40)).filter(lambda t: t[0] != t[1]))
+def test_phi4_ens_heun_random_shapes(gpu, oracle_mod, bm_tables, shape, steps, every, C, seed, dtau, m2, lam, step0):
+    """The ensemble's Heun step at random legal shapes over all four K, two
+    replicas with different Δτ, m², λ, seeds and start counters (up to 2^40):
+    bit for bit the oracle's Heun entry (oracle.phi4_heun_step; at C = 1 with
+    the device's Box-Muller factors), the counters advanced by `steps`, no
+    guard flag; the series rows within 2 n u Σ|t| of the exactly rounded sums
+    of the oracle's field at that step."""
+    import contextlib
+    from stochquant_amd import Phi4Ensemble
+    from test_gpu_phi4_ens import _exact_sums
+    info = Phi4Ensemble.shape_info(shape)                  # raises if the strategy left the legal shapes
+    seeds = [seed, seed + 12345]
+    ps = [oracle_mod.phi4_params(shape, dtau[r], m2[r], lam[r], seeds[r], C=C) for r in range(2)]
+    mode = oracle_mod.device_transcendentals(bm_tables) if C else contextlib.nullcontext()
+    with mode:
+        ref = [oracle_mod.phi4_init(ps[r], 0.8) for r in range(2)]
+        with Phi4Ensemble(shape, 2, dtau=dtau, m2=m2, lam=lam, C=C, seeds=seeds) as E:
+            E.upload(np.stack(ref))
+            E.step_counter = list(step0)
+            ser = E.step(steps, every=every, scheme="heun")
+            got = E.download()
+            assert [int(s) for s in E.step_counter] == [s + steps for s in step0]
+            assert not E.flags().any()
+        assert (ser is None) if every == 0 else (ser.shape == (steps // every, 2, 4))
+        for r in range(2):
+            for s in range(steps):
+                ref[r], mx = oracle_mod.phi4_heun_step(ps[r], ref[r], step0[r] + s)
+                assert max(mx) < ps[r].clampv
+                if every and (s + 1) % every == 0:
+                    exact, bound, _ = _exact_sums(ref[r])
+                    err = np.abs(ser[(s + 1) // every - 1, r] - exact)
+                    assert np.all(err <= bound), (shape, info, r, s, err, bound)
+            assert np.array_equal(got[r].view(np.uint32), ref[r].view(np.uint32)), \
+                (shape, info, r, C, step0, np.max(np.abs(got[r] - ref[r])))
 
 
 def _exact(res):

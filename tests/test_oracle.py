@@ -123,6 +123,176 @@ def test_phi4_slab_decomposition_matches_monolithic(oracle_mod):
         assert np.array_equal(np.concatenate(parts), ref)
 
 
+# ---- the Heun entry (orc_phi4_heun_step); the helpers are shared with tests/test_gpu_phi4_ens_heun_oracle.py ----
+
+HEUN_CLAMP = 1000.0
+
+
+def np_guard(a, clamp=HEUN_CLAMP):
+    """The update's guard on float32 values: NaN -> +clamp, else clipped to [-clamp, clamp]."""
+    cl = np.float32(clamp)
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isnan(a), cl, np.minimum(np.maximum(a, -cl), cl)).astype(np.float32)
+
+
+def same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+def heun_by_composition(oracle_mod, p, phi, step):
+    """The header's definition out of the Euler entry: two phi4_step at one counter, the average as one float32
+    add and one float32 multiply in NumPy, the guard; the maxima after each guard."""
+    phi = np.ascontiguousarray(phi, dtype=np.float32)
+    s1 = oracle_mod.phi4_step(p, phi, step)
+    s2 = oracle_mod.phi4_step(p, s1, step)
+    with np.errstate(invalid="ignore", over="ignore"):
+        avg = np.float32(0.5) * (phi + s2)
+    assert avg.dtype == np.float32
+    out = np_guard(avg, p.clampv)
+    return out, tuple(np.abs(a).max() for a in (s1, s2, out))
+
+
+# The guard flag stage by stage: C = 0, clamp 1000, one Heun step at counter 0.  (name, start value, value of the
+# site (Lz-1, Ly-1, Lx-1) or None, (dtau, m2, lam), (max|p|, max|e|, max|phi'|), flag, shapes).  Which maximum
+# reaches the clamp: none; |e| alone; |p| and |e|; |p| alone.  The last needs six distinct neighbours of the odd
+# site (Ly, Lz >= 3), and its values do not depend on the shape beyond that.
+HEUN_GUARD_CASES = [
+    ("quiet", 10.0, None, (0.05, 0.0, 1.2), (0.0, 0.0, 5.0), False, [(8, 2, 2), (32, 32, 32)]),
+    ("stage2", 40.0, None, (0.05, 0.0, 1.2), (600.0, 1000.0, 520.0), True, [(8, 2, 2), (32, 32, 32)]),
+    ("both", 55.0, None, (0.05, 0.0, 1.2), (1000.0, 1000.0, 527.5), True, [(8, 2, 2), (32, 32, 32)]),
+    ("stage1", 999.0, 900.0, (0.2, 0.05, 0.0), (1000.0, 985.476, 992.238), True,
+     [(8, 8, 8), (32, 32, 32), (64, 11, 29)]),
+]
+HEUN_GUARD_PARAMS = [(c, s) for c in HEUN_GUARD_CASES for s in c[6]]
+HEUN_GUARD_IDS = [f"{c[0]}-{s[0]}x{s[1]}x{s[2]}" for c, s in HEUN_GUARD_PARAMS]
+
+
+def heun_guard_field(case, shape):
+    Lx, Ly, Lz = shape
+    phi = np.full((Lz, Ly, Lx), case[1], dtype=np.float32)
+    if case[2] is not None:
+        phi[Lz - 1, Ly - 1, Lx - 1] = case[2]
+    return phi
+
+
+def assert_heun_guard_maxima(case, maxima):
+    """The oracle's maxima are the table's: a clamp is met exactly, the other values to the table's digits
+    (5e-4 absolute on values of order 1000 is 8 ulp of float32; the quiet case's |p|, |e| are roundings of
+    10 - 10, below 1e-4).  So a change to the recipe cannot turn a guard test into one where nothing fires."""
+    for got, want in zip(maxima, case[4]):
+        if want == HEUN_CLAMP:
+            assert got == np.float32(HEUN_CLAMP), (case[0], maxima)
+        else:
+            assert got < HEUN_CLAMP and abs(float(got) - want) <= (1e-4 if want == 0.0 else 5e-4), (case[0], maxima)
+    assert any(m >= HEUN_CLAMP for m in maxima) == case[5], (case[0], maxima)
+
+
+@pytest.mark.parametrize("C", [0.0, 1.0])
+@pytest.mark.parametrize("shape", [(8, 2, 2), (32, 8, 13), (32, 32, 32)])
+def test_phi4_heun_step_is_the_composition(oracle_mod, shape, C):
+    """Three steps from a counter above 2^32, field and maxima bit for bit; then one step from a field with a
+    NaN and a site at 5000, where only the final guard keeps the average inside the clamp."""
+    p = oracle_mod.phi4_params(shape, 0.03, 0.5, 2.0, 0xDEADBEEF12345, clamp=HEUN_CLAMP, C=C)
+    a = b = oracle_mod.phi4_init(p, 0.7)
+    s0 = 2 ** 32 + 7
+    for k in range(3):
+        a, ma = oracle_mod.phi4_heun_step(p, a, s0 + k)
+        b, mb = heun_by_composition(oracle_mod, p, b, s0 + k)
+        assert same_bits(a, b), (k, np.count_nonzero(a != b))
+        assert a.dtype == np.float32 and a.shape == (shape[2], shape[1], shape[0])
+        assert all(np.float32(x) == np.float32(y) for x, y in zip(ma, mb)), (k, ma, mb)
+        assert max(ma) < 10.0
+    if C:   # the noise is that of the counter: another counter gives another field
+        assert not same_bits(oracle_mod.phi4_heun_step(p, b, s0)[0], oracle_mod.phi4_heun_step(p, b, s0 + 1)[0])
+    bad = np.array(b)
+    bad[shape[2] - 1, 1, 3] = np.float32("nan")
+    bad[0, shape[1] - 1, shape[0] - 1] = np.float32(5000.0)
+    got, mg = oracle_mod.phi4_heun_step(p, bad, s0)
+    want, mw = heun_by_composition(oracle_mod, p, bad, s0)
+    assert same_bits(got, want)
+    assert got[shape[2] - 1, 1, 3] == np.float32(HEUN_CLAMP) and got[0, shape[1] - 1, shape[0] - 1] == HEUN_CLAMP
+    assert not np.isnan(got).any() and np.abs(got).max() == HEUN_CLAMP
+    assert [float(x) for x in mg] == [float(x) for x in mw] and float(mg[2]) == HEUN_CLAMP, (mg, mw)
+
+
+@pytest.mark.parametrize("case,shape", HEUN_GUARD_PARAMS, ids=HEUN_GUARD_IDS)
+def test_phi4_heun_guard_maxima(oracle_mod, case, shape):
+    dt, m2, lam = case[3]
+    p = oracle_mod.phi4_params(shape, dt, m2, lam, 1, clamp=HEUN_CLAMP, C=0.0)
+    phi = heun_guard_field(case, shape)
+    out, mx = oracle_mod.phi4_heun_step(p, phi, 0)
+    assert_heun_guard_maxima(case, mx)
+    ref, mr = heun_by_composition(oracle_mod, p, phi, 0)
+    assert same_bits(out, ref) and [float(x) for x in mx] == [float(x) for x in mr]
+
+
+# Convergence order against a float64 solution: noise off, so the step integrates the ODE
+# dphi/dtau = lap phi - phi (m2 + lam phi^2 / 6).
+ODE_M2, ODE_LAM, ODE_T, ODE_SEED, ODE_AMP = 0.5, 1.0, 0.8, 5, 0.8
+ODE_SHAPES = [(8, 2, 2), (8, 8, 8), (32, 8, 13)]
+_ode_cache = {}
+
+
+def ode_params(oracle_mod, shape, n):
+    return oracle_mod.phi4_params(shape, ODE_T / n, ODE_M2, ODE_LAM, ODE_SEED, clamp=HEUN_CLAMP, C=0.0)
+
+
+def ode_start_and_reference(oracle_mod, shape):
+    """(start field, phi(T) in float64): classical RK4 in NumPy float64, 4000 steps (its own error is of order
+    (T / 4000)^4, some 1e-14: nothing beside the 1e-4 and more measured against it).  Once per shape."""
+    if shape not in _ode_cache:
+        phi0 = oracle_mod.phi4_init(ode_params(oracle_mod, shape, 16), ODE_AMP)
+
+        def F(x):
+            nb = sum(np.roll(x, 1, axis=ax) + np.roll(x, -1, axis=ax) for ax in range(3))
+            return nb - 6.0 * x - x * (ODE_M2 + ODE_LAM * x * x / 6.0)
+
+        x, h = phi0.astype(np.float64), ODE_T / 4000
+        for _ in range(4000):
+            k1 = F(x)
+            k2 = F(x + 0.5 * h * k1)
+            k3 = F(x + 0.5 * h * k2)
+            k4 = F(x + h * k3)
+            x = x + (h / 6.0) * (k1 + 2.0 * k2 + 2.0 * k3 + k4)
+        phi0.setflags(write=False)
+        x.setflags(write=False)
+        _ode_cache[shape] = (phi0, x)
+    return _ode_cache[shape]
+
+
+def assert_ode_orders(tag, shape, err):
+    """err[scheme][n] = max |phi_n - reference|: print the figures, then the bounds.  The nearest wrong answers
+    are order 1 (a Heun step that lost its second stage or its average) and order 3."""
+    order = {s: float(np.log2(err[s][16] / err[s][32])) for s in ("heun", "euler")}
+    for s in ("heun", "euler"):
+        print(f"ORDER {s} {tag} {shape}: err_16 {err[s][16]:.4e} err_32 {err[s][32]:.4e} order {order[s]:.3f}",
+              flush=True)
+    assert 1.8 <= order["heun"] <= 2.5, (shape, order, err)
+    assert 0.8 <= order["euler"] <= 1.2, (shape, order, err)
+    assert err["heun"][32] < err["euler"][32] / 10.0, (shape, err)
+    return order
+
+
+@pytest.mark.parametrize("shape", ODE_SHAPES)
+def test_phi4_heun_is_second_order_on_the_interacting_drift(oracle_mod, shape):
+    """m2 = 0.5, lam = 1, C = 0 from phi4_init(seed 5, amp 0.8) to T = 0.8 in n = 16 and n = 32 steps against
+    the float64 RK4 solution; order = log2(err_16 / err_32).  Measured (8x2x2 / 8x8x8 / 32x8x13): Heun order
+    2.14 / 2.16 / 2.17 with err_32 2.4e-4 .. 4.4e-4, more than 100 x the accumulated fp32 rounding (32 steps
+    of some 1e-7), so the order is the scheme's; Euler order 0.965 / 0.970 / 0.963 with err_32 6.1e-3 ..
+    1.1e-2.  Asserted: Heun in [1.8, 2.5], Euler in [0.8, 1.2], Heun err_32 < Euler err_32 / 10."""
+    phi0, ref = ode_start_and_reference(oracle_mod, shape)
+    err = {"heun": {}, "euler": {}}
+    for n in (16, 32):
+        p = ode_params(oracle_mod, shape, n)
+        h, e = phi0, phi0
+        for s in range(n):
+            h = oracle_mod.phi4_heun_step(p, h, s)[0]
+            e = oracle_mod.phi4_step(p, e, s)
+        err["heun"][n] = float(np.max(np.abs(h - ref)))
+        err["euler"][n] = float(np.max(np.abs(e - ref)))
+    assert_ode_orders("oracle", shape, err)
+
+
 def test_serial_reference_order_matches_exact_gauss_seidel_law(oracle_mod, tmp_path):
     """The reference semantics (serial restatement) relax to the exact
     stationary law of the Gauss-Seidel-left Euler chain (tests/qm1d_exact.py):
