@@ -592,12 +592,49 @@ int sq_phi4_ens_pcorr_shape_info(const int dims[3], int out[6]);
  * adds (M = 0: SQ_E_STATE), both bits what its correlate != 0 adds; with
  * either bit every >= 1, else SQ_E_ARG; other bits: SQ_E_ARG.  nsteps = 0 does
  * nothing.  sq_phi4_ens_perf counts one step (and `sites` site updates) per
- * Heun step, although each does the work of two.  Frames
- * (sq_phi4_ens_run_frames*) always take Euler steps.  SQ_SCHEME_*: the names
- * of the two integrators (Phi4Ensemble.step's "euler" / "heun"). */
+ * Heun step, although each does the work of two.  SQ_SCHEME_*: the names
+ * of the two integrators (Phi4Ensemble.step's and run_frames' "euler" /
+ * "heun").
+ *
+ * sq_phi4_ens_run_frames_heun: frames of Heun steps.  A Heun frame of replica
+ * r is the Euler frame of sq_phi4_ens_run_frames with every step replaced by
+ * one Heun step as above; the counter advances by one per Heun step and by
+ * `loops` per frame, whatever the verdict.  The step's record (M, D, A):
+ *   M = max over sites of phi', signed;
+ *   D = the largest, over the sites attaining M, of
+ *       fabsf(fmaf(-sigq, xi, phi' - phi)), phi the Heun step's input, xi the
+ *       step's normal, sigq = 0 in the noise-off instance: the Heun step's
+ *       drift increment dtau/2 (F(phi) + F(p)) where the Euler record has
+ *       dtau F(phi).  If the step's input holds a NaN, D's bits are
+ *       unspecified; the verdict is not, because the guard flag settles it;
+ *   A = max(max |p|, max |e|, max |phi'|), each taken after its guard, hence
+ *       <= clamp; the frame's guard flag is A >= clamp at any executed step.
+ * Everything else is the Euler frame's, unchanged and shared: fired = M > T &&
+ * D > V, then T = M, V = max(V, A); the early exit at the firing step; stable
+ * = no guard trip && not fired; the controller on the double dtau; the new
+ * coefficients; the snapshot on a stable frame and the reload from it on an
+ * unstable one; the frame state (T and V from the start field at a replica's
+ * first frame); the records, valid through the firing step
+ * (sq_phi4_ens_stability returns the Heun records after a Heun call); `series`
+ * after every verdict; the measurements after stable frames only.  measure:
+ * bit 0 adds what sq_phi4_ens_run_frames_corr adds, bit 1 what
+ * sq_phi4_ens_run_frames_pcorr adds (M = 0: SQ_E_STATE), both bits what its
+ * correlate != 0 adds; other bits or a null handle: SQ_E_ARG.  The other
+ * argument rules are those of sq_phi4_ens_run_frames.  Euler and Heun frames
+ * calls and raw steps of either scheme alternate freely on one handle and
+ * share T, V, the controller's count and dtau.  sq_phi4_ens_perf counts one
+ * step per executed Heun step.
+ *
+ * sq_phi4_ens_heun_frames_shape_info (no device, no handle): out = {LDS images
+ * and dynamic LDS bytes of the plain Heun frames launch (those of the frames
+ * launch in sq_phi4_ens_shape_info), a mask whose bit m is set when measure =
+ * m runs on this shape (0xf, or 0x3 for a shape that cannot hold momenta), 0};
+ * SQ_E_ARG exactly where sq_phi4_ens_shape_info gives it. */
 #define SQ_SCHEME_EULER 0
 #define SQ_SCHEME_HEUN 1
 int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series, int measure);
+int sq_phi4_ens_run_frames_heun(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, int measure);
+int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]);
 
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */

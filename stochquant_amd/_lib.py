@@ -208,6 +208,8 @@ SIGNATURES = {
     "sq_phi4_ens_pslices": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D]),
     "sq_phi4_ens_pcorrelator": (ctypes.c_int, [_P, _D, _D, ctypes.c_int, _I]),
     "sq_phi4_ens_pcorr_shape_info": (ctypes.c_int, [_I, _I]),
+    "sq_phi4_ens_run_frames_heun": (ctypes.c_int, [_P, ctypes.c_int, _I, _D, _D, ctypes.c_int]),
+    "sq_phi4_ens_heun_frames_shape_info": (ctypes.c_int, [_I, _I]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 

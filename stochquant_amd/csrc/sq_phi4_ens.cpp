@@ -415,7 +415,7 @@ int sq_phi4_ens_step_corr(sq_phi4_ens *e, int nsteps, int every, double *series)
 
 namespace {
 int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr,
-                   bool pcorr = false);
+                   bool pcorr = false, bool heun = false);
 }
 
 int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
@@ -430,7 +430,10 @@ int sq_phi4_ens_run_frames_corr(sq_phi4_ens *e, int nframes, int *stable, double
 
 namespace {
 
-int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr, bool pcorr) {
+// heun: the same call with the Heun frames kernel (sq_phi4_ens_run_frames_heun); one Heun step counts as one
+// step everywhere on the host.
+int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr, bool pcorr,
+                   bool heun) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
     if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
@@ -481,7 +484,12 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
     f.nframes = nframes;
     f.loops = L;
     f.adapt = e->p.adapt_dtau ? 1 : 0;
-    if (pcorr) SQ_HIP(sq::phi4_ens_frames_pcorr_launch(a, f, ens_pcorr_args(e, corr), e->R, e->stream));
+    if (heun) {
+        const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+        const sq::Phi4EnsPCorrArgs p = pcorr ? ens_pcorr_args(e, corr) : sq::Phi4EnsPCorrArgs{};
+        SQ_HIP(sq::phi4_ens_heun_frames_launch(a, f, (corr && !pcorr) ? &c : nullptr, pcorr ? &p : nullptr, e->R,
+                                               e->stream));
+    } else if (pcorr) SQ_HIP(sq::phi4_ens_frames_pcorr_launch(a, f, ens_pcorr_args(e, corr), e->R, e->stream));
     else if (corr) SQ_HIP(sq::phi4_ens_frames_corr_launch(a, f, ens_corr_args(e), e->R, e->stream));
     else SQ_HIP(sq::phi4_ens_frames_launch(a, f, e->R, e->stream));
     e->launches++;
@@ -684,6 +692,24 @@ int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series,
 int sq_phi4_ens_run_frames_pcorr(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series,
                                  int correlate) {
     return ens_run_frames(e, nframes, stable, dtau, series, correlate != 0, true);
+}
+
+int sq_phi4_ens_run_frames_heun(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series,
+                                int measure) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (measure & ~3) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) and bit 1 (momenta) only");
+    return ens_run_frames(e, nframes, stable, dtau, series, (measure & 1) != 0, (measure & 2) != 0, true);
+}
+
+int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
+    out[0] = s.fr_two ? 2 : 1;
+    out[1] = s.fr_lds_bytes;
+    out[2] = s.pc_ok ? 0xf : 0x3;  // bit m: measure = m runs on this shape; momenta need their LDS region
+    out[3] = 0;
+    return SQ_OK;
 }
 
 int sq_phi4_ens_pcorr_sums(sq_phi4_ens *e, int first, int count, double *G, long long *nmeas) {

@@ -4,7 +4,9 @@
 // per lattice, the field on-chip between the call's first and last step.
 // Raw steps (phi4_ens_step_launch) or whole frames decided in the kernel
 // (phi4_ens_frames_launch: per replica the stability rule, the rollback and
-// the Δτ controller of DESIGN.md §7).  Not installed.
+// the Δτ controller of DESIGN.md §7), either with Euler steps or with
+// second-order Heun steps (phi4_ens_heun_launch, phi4_ens_heun_frames_launch).
+// Not installed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -147,6 +149,13 @@ hipError_t phi4_ens_pslices_launch(const Phi4EnsArgs &a, const Phi4EnsPCorrArgs 
 // the LDS layout and the argument rules are those of the three step launches.
 hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, const Phi4EnsPCorrArgs *p, int nrep,
                                 hipStream_t s);
+// nframes frames of Heun steps of every replica in one launch (phi4_ens_heun_frames_kernel): the frames launch
+// with every step the Heun step above, the step's record taken of phi' against the step's input (DESIGN.md
+// §4.3).  c, p nullable, at most one of them: the measurements of phi4_ens_frames_corr_launch /
+// phi4_ens_frames_pcorr_launch after every stable frame.  The work-group shape, the LDS layout and the argument
+// rules are those of the three frames launches; the image count selects the instance.
+hipError_t phi4_ens_heun_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs *c,
+                                       const Phi4EnsPCorrArgs *p, int nrep, hipStream_t s);
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

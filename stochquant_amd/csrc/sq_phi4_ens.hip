@@ -43,6 +43,9 @@
 // phi4_ens_heun_kernel is the step kernel with the second-order stochastic
 // Heun step in place of the Euler one: phi' = guard(0.5 (phi + E(E(phi)))), E
 // the update above applied twice with the normals of one counter (ens_heun).
+// phi4_ens_heun_frames_kernel runs whole frames of such steps: the frames
+// kernel's rule, exit, verdict, controller and snapshot around ens_heun, the
+// step's record taken of phi' against the Heun step's input.
 #define SQ_PHI4_KERNELS_ONLY
 #include <type_traits>
 
@@ -174,20 +177,23 @@ __device__ __forceinline__ double ens_wave_sum(double v) {
 // of wave 0 folds sum i over the waves in wave order into out[i] (and lane 4
 // the maximum into out[4] when mxout): the same bits on every call.  The
 // scratch is free again after the next block barrier, which every later
-// writer sits behind.
-__device__ __forceinline__ void ens_fold(double (&s)[4], float mx, double *scr, double *out, bool mxout) {
+// writer sits behind.  tid: the lane's threadIdx.x; a caller with no register
+// to spare passes an opaque copy, so that nothing formed from it here is
+// hoisted out of the caller's loops and kept (ens_corr, ens_pcorr_measure alike).
+__device__ __forceinline__ void ens_fold(double (&s)[4], float mx, double *scr, double *out, bool mxout,
+                                         unsigned tid = threadIdx.x) {
     float *scm = reinterpret_cast<float *>(scr + 16 * 4);
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const int w = tid >> 6, nw = blockDim.x >> 6;
 #pragma unroll
     for (int i = 0; i < 4; ++i) s[i] = ens_wave_sum(s[i]);
     mx = dpp_all_max_f(mx);  // never NaN: fmaxf of magnitudes drops them
-    if ((threadIdx.x & 63) == 0) {
+    if ((tid & 63) == 0) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) scr[4 * w + i] = s[i];
         scm[w] = mx;
     }
     __syncthreads();
-    const int i = threadIdx.x;
+    const int i = tid;
     if (i < 4) {
         double t = 0.0;
 #pragma unroll
@@ -213,11 +219,11 @@ __device__ __forceinline__ void ens_fold(double (&s)[4], float mx, double *scr, 
 // again after the next block barrier.
 template <bool ACC>
 __device__ __forceinline__ void ens_corr(const EnsGeo &g, int Lz, const float *img, double *Sl, double *G, double *S1,
-                                         long long *nm, double *Sout) {
+                                         long long *nm, double *Sout, unsigned tid = threadIdx.x) {
 #pragma clang fp contract(off)
     const float4 *img4 = reinterpret_cast<const float4 *>(img);
-    const int T = blockDim.x, lane = threadIdx.x & 63, nw = T >> 6;
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int T = blockDim.x, lane = tid & 63, nw = T >> 6;
+    const int w = __builtin_amdgcn_readfirstlane((int)(tid >> 6));
     for (int z = w; z < Lz; z += nw) {  // wave-uniform: every lane reaches the scan
         const float4 *sl = img4 + z * g.qplane;
         double a = 0.0;
@@ -230,7 +236,7 @@ __device__ __forceinline__ void ens_corr(const EnsGeo &g, int Lz, const float *i
     }
     __syncthreads();
     const int nt = Lz / 2 + 1;
-    for (int t = threadIdx.x; t < nt; t += T) {
+    for (int t = tid; t < nt; t += T) {
         double old = 0.0;
         if (ACC) old = G[t];
         double acc = 0.0;
@@ -242,14 +248,14 @@ __device__ __forceinline__ void ens_corr(const EnsGeo &g, int Lz, const float *i
         G[t] = ACC ? __dadd_rn(old, acc) : acc;
     }
     if (ACC) {
-        if ((int)threadIdx.x == T - 1) {
+        if ((int)tid == T - 1) {
             double s = 0.0;
             for (int z = 0; z < Lz; ++z) s = __dadd_rn(s, Sl[z]);
             *S1 = __dadd_rn(*S1, s);
             *nm += 1;
         }
     } else if (Sout != nullptr) {
-        for (int z = threadIdx.x; z < Lz; z += T) Sout[z] = Sl[z];
+        for (int z = tid; z < Lz; z += T) Sout[z] = Sl[z];
     }
 }
 
@@ -379,10 +385,12 @@ __device__ __forceinline__ Phi4EnsPCorrArgs ens_pcorr_args(const CA &...c) {
 // The replica's momentum measurement where its zero-momentum one sits: that one
 // first when P.corr is given, both through the region at Pl.
 __device__ __forceinline__ void ens_pcorr_measure(const EnsGeo &g, const Phi4EnsArgs &E, int r, const float *img,
-                                                  double *Pl, const Phi4EnsPCorrArgs &P) {
+                                                  double *Pl, const Phi4EnsPCorrArgs &P,
+                                                  unsigned tid = threadIdx.x) {
     const int nt = E.Lz / 2 + 1;
     if (P.corr.G != nullptr)  // block-uniform
-        ens_corr<true>(g, E.Lz, img, Pl, P.corr.G + (size_t)r * (size_t)nt, P.corr.S1 + r, P.corr.nmeas + r, nullptr);
+        ens_corr<true>(g, E.Lz, img, Pl, P.corr.G + (size_t)r * (size_t)nt, P.corr.S1 + r, P.corr.nmeas + r, nullptr,
+                       tid);
     ens_pcorr<true>(g, E.Ly, E.Lz, img, Pl, P, P.Gp + (size_t)r * (size_t)(P.M * nt), P.nmeas_p + r, nullptr);
 }
 
@@ -483,6 +491,48 @@ struct EnsFlagsPk {
     }
 };
 
+// A wave's record of one Heun step.  Where FrameAcc carries the running (m, d)
+// in every lane, this one carries the wave's maximum key in scalars: the K = 8
+// instances of phi4_ens_heun_frames_kernel have no two registers for them.
+struct EnsHeunAcc {
+    float am;                // per lane: max |p|, |e|, |phi'| after their guards
+    unsigned long long key;  // wave-uniform: max over the wave's sites so far of ord(phi') << 32 | bits(d); 0: none
+    float mw;                // wave-uniform: the phi' of key, -inf before the first site
+};
+
+// ens_frame_sites (below) for a Heun step: the record of the lane's float4 o =
+// phi' against the step's input c = phi, both in registers, and the step's
+// normals xi: d = |fma(-sigq, xi, phi' - phi)|, the Heun step's drift increment
+// h/2 (F(phi) + F(p)) where the Euler record has h F(phi).  mo: max |phi'| of o
+// after the guard, 0 in a lane without the quad, whose o is -inf.  A float4
+// below the wave's running maximum can neither set nor tie the step's; where
+// some lane's reaches it, the lanes take their four sites by stab_site from
+// (-inf, 0) and the wave's largest key joins f.key: every site that reaches the
+// final maximum was at or above the running one when its quad came, so the key
+// is exact.  Every lane of the wave calls it.
+template <bool NZ>
+__device__ __forceinline__ void ens_heun_sites(const Phi4StepArgs &A, EnsHeunAcc &f, uint32_t fl, const float4 &o,
+                                               const float4 &c, const f32x4n &xi, float mo) {
+    f.am = vmax(f.am, mo);
+    if (__ballot(mo >= f.mw) == 0ull) return;  // max |o| >= max o
+    const float o4 = vmax(vmax3(o.x, o.y, o.z), o.w);  // the guard's output: never NaN
+    if (__ballot(o4 >= f.mw) == 0ull) return;
+    FrameAcc t = frame_acc();
+    asm volatile("" : "+v"(fl));
+    if (fl & kEnsValid) {
+        const float s = NZ ? A.sigq : 0.f;
+        stab_site(t, o.x, c.x, xi.a, s);
+        stab_site(t, o.y, c.y, xi.b, s);
+        stab_site(t, o.z, c.z, xi.c, s);
+        stab_site(t, o.w, c.w, xi.d, s);
+    }
+    const unsigned long long k = dpp_all_max_u64(((unsigned long long)ord_f32(t.m) << 32) | __float_as_uint(t.d));
+    if (k > f.key) {  // wave-uniform
+        f.key = k;
+        f.mw = unord_f32_dev((uint32_t)(k >> 32));
+    }
+}
+
 // One stochastic Heun step of the lane's K quads: with E the
 // update of ens_step at counter s, c <- guard(0.5 (c + E(E(c)))), both
 // applications with the normals of s.  The lane keeps phi in c throughout;
@@ -503,10 +553,16 @@ struct EnsFlagsPk {
 // KEEP: the normals of stage 1 stay in registers for stage 2 (4 K VGPRs);
 // otherwise stage 2 evaluates tb_noise again: the same counter and key, so
 // the same bits.  am takes max |p|, max |e| and max |phi'|, each after its guard.
-template <int K, bool NZ, bool TWO>
+//
+// FR (phi4_ens_heun_frames_kernel): stage 2 also takes the step's stability
+// record into *fa (ens_heun_sites), where phi (the lane's registers), the
+// normals and phi' are at hand together; am is fa->am; the quads of lanes
+// without one hold -inf, as for ens_step_fr; and the step's last barrier is the
+// caller's, which posts the wave's record before it.
+template <int K, bool NZ, bool TWO, bool FR = false>
 __device__ __forceinline__ void ens_heun(const Phi4StepArgs &A, const EnsGeo &g, float4 (&c)[K],
                                          const EnsFlagsPk<K> &fl, float *cur, float *oth, uint32_t slo, uint32_t shi,
-                                         float &am) {
+                                         float &am, EnsHeunAcc *fa = nullptr) {
     constexpr bool KEEP = NZ && K <= 4;
     const int T = blockDim.x;
     f32x4n xk[KEEP ? K : 1] = {};
@@ -559,7 +615,32 @@ __device__ __forceinline__ void ens_heun(const Phi4StepArgs &A, const EnsGeo &g,
             uint32_t f = fl.get(j);
             int q = (int)threadIdx.x + j * T;
             asm volatile("" : "+v"(f), "+v"(q));
-            if (f & kEnsValid) {
+            if constexpr (FR) {
+                const float4 phi = c[j];  // -inf in a lane without this quad: so is its phi' below
+                f32x4n xi{};
+                float mo = 0.f;
+                if (f & kEnsValid) {
+                    const EnsNbr n = ens_nbr(g, q, f);
+                    const float4 p = img4[q];
+                    const float4 up = img4[n.up], dn = img4[n.dn], zm = img4[n.zm], zp = img4[n.zp];
+                    const float lft = img[n.lf], rgt = img[n.rg];
+                    if constexpr (KEEP) xi = xk[j];
+                    else xi = tb_noise<NZ>(A, 0u, (uint32_t)q, slo, shi);
+                    float mp;
+                    const float4 e =
+                        site_update4<NZ>(p, lft, rgt, up, dn, zm, zp, xi, A, false, f32x2{A.m2, A.m2}, &mp);
+                    float4 o;
+                    o.x = ens_guard(__fmul_rn(0.5f, __fadd_rn(phi.x, e.x)), cl);
+                    o.y = ens_guard(__fmul_rn(0.5f, __fadd_rn(phi.y, e.y)), cl);
+                    o.z = ens_guard(__fmul_rn(0.5f, __fadd_rn(phi.z, e.z)), cl);
+                    o.w = ens_guard(__fmul_rn(0.5f, __fadd_rn(phi.w, e.w)), cl);
+                    c[j] = o;
+                    mo = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)));  // never NaN
+                    am = fmaxf(am, mp);
+                    if constexpr (TWO) cur4[q] = o;
+                }
+                ens_heun_sites<NZ>(A, *fa, f, c[j], phi, xi, mo);
+            } else if (f & kEnsValid) {
                 const EnsNbr n = ens_nbr(g, q, f);
                 const float4 p = img4[q];
                 const float4 up = img4[n.up], dn = img4[n.dn], zm = img4[n.zm], zp = img4[n.zp];
@@ -587,7 +668,7 @@ __device__ __forceinline__ void ens_heun(const Phi4StepArgs &A, const EnsGeo &g,
                 if (fl.get(j) & kEnsValid) cur4[(int)threadIdx.x + j * T] = c[j];
         }
     }
-    __syncthreads();  // phi' is in cur
+    if constexpr (!FR) __syncthreads();  // phi' is in cur
 }
 
 // phi4_ens_step_kernel with ens_heun as its step (sq_phi4_ens_step_heun): the
@@ -931,6 +1012,212 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_kernel(const
     }
 }
 
+// phi4_ens_frames_kernel with ens_heun as its step (sq_phi4_ens_run_frames_heun,
+// DESIGN.md §4.3): the same frame state, rule, controller, snapshot, records,
+// series and measurements, the counter advancing by one per Heun step and by
+// loops per frame.  The step's record comes from ens_heun's stage 2; the wave's
+// key and maximum go to the rotating slot before the step's last barrier, which
+// stands here, and are read behind it: no barrier beyond ens_heun's two (TWO)
+// or four.  TWO is a template parameter: cur is img0 for the whole call, and the
+// one-image K = 8 instances have no register for a run-time choice.
+//
+// LDS hazards.  Within a step they are ens_heun's: TWO, stage 1 reads cur and
+// writes oth, barrier, stage 2 reads oth and writes cur, barrier; one image,
+// stage 1 reads it, barrier, the lanes exchange their own quads, barrier, stage 2
+// reads it, barrier, phi' to it, barrier.  Behind a step's last barrier no wave
+// reads an image before stage 1 of the next step (the record slots, the scratch
+// and the measurement regions lie behind the images), and stage 1 never writes
+// cur.  So the snapshot reload, which follows the frame's last executed step,
+// writes the lane's own quads of cur with no wave reading them, and its own
+// barrier puts them in front of every later reader: ens_sums, the measurement
+// and the next frame's stage 1.
+template <int K, bool TWO, typename... CA>
+__global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_heun_frames_kernel(const Phi4EnsArgs E,
+                                                                                 const Phi4EnsFrameArgs F,
+                                                                                 const CA... ca) {
+    constexpr bool PC = kEnsPCorr<CA...>;
+    constexpr bool CORR = sizeof...(CA) != 0;  // either kind of measurement
+    const int r = blockIdx.x;
+    const EnsGeo g = ens_geo(E);
+    const Phi4EnsRec rc = E.rec[r];
+    const Phi4EnsFrameState st = F.st[r];
+    Phi4StepArgs A{};
+    A.h = rc.h;
+    A.m2 = rc.m2;
+    A.lam6 = rc.lam6;
+    A.sig = rc.sig;
+    A.sigq = rc.sigq;
+    A.clampv = E.clampv;
+    A.k0 = rc.k0;
+    A.k1 = rc.k1;
+    const bool nz = rc.sig != 0.0f;
+    float *cur = reinterpret_cast<float *>(ens_smem);
+    float *oth = TWO ? cur + 4 * g.Q : cur;
+    char *sb = ens_smem + (size_t)(TWO ? 2 : 1) * 16 * (size_t)g.Q;
+    unsigned long long *fk = reinterpret_cast<unsigned long long *>(sb + kPhi4EnsScratchBytes);  // [3]
+    uint32_t *fw = reinterpret_cast<uint32_t *>(fk + 3);  // [0..2] a step's maximum, [3], [4] the start field's
+    if (threadIdx.x < 3) fk[threadIdx.x] = 0ull;
+    if (threadIdx.x < 5) fw[threadIdx.x] = 0u;
+    float4 c[K];
+    EnsFlagsPk<K> fl;
+    float sT = st.T, sV = st.V;
+    {
+        uint32_t f[K];
+        ens_load<K>(E, g, r, c, f, cur);  // ends in a barrier
+        fl.pack(f);
+        float mp = -__builtin_inff(), ma = 0.f;  // max phi and max |phi| of the start field (the first frame ever)
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (f[j] & kEnsValid) {
+                mp = fmaxf(mp, fmaxf(fmaxf(c[j].x, c[j].y), fmaxf(c[j].z, c[j].w)));
+                ma = fmaxf(ma, fmaxf(fmaxf(fabsf(c[j].x), fabsf(c[j].y)), fmaxf(fabsf(c[j].z), fabsf(c[j].w))));
+            } else {
+                c[j].x = c[j].y = c[j].z = c[j].w = -__builtin_inff();  // ens_heun<FR>
+            }
+        }
+        if (!st.init) {
+            mp = dpp_all_max_f(mp);
+            ma = dpp_all_max_f(ma);
+            if ((threadIdx.x & 63) == 0) {
+                atomicMax(&fw[3], ord_f32(mp));
+                atomicMax(&fw[4], __float_as_uint(ma));
+            }
+            __syncthreads();
+            sT = unord_f32_dev(fw[3]);
+            sV = __uint_as_float(fw[4]);
+        }
+    }
+    sT = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sT)));
+    sV = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(sV)));
+    double dtau = st.dtau;
+    int cnt = st.cnt, fired = -1, gflag = 0, exec = 0, sticky = 0;
+    int slot = 0;
+    const unsigned long long s0 = rc.step + E.adv;
+    for (int f = 0; f < F.nframes; ++f) {
+        fired = -1;
+        gflag = 0;
+        const unsigned long long sf = s0 + (unsigned long long)f * (unsigned long long)F.loops;
+        for (int t = 0; t < F.loops; ++t) {
+            const unsigned long long s = sf + (unsigned long long)t;
+            const uint32_t slo = (uint32_t)s, shi = (uint32_t)(s >> 32);
+            EnsHeunAcc fa{0.f, 0ull, -__builtin_inff()};
+            if (nz) ens_heun<K, true, TWO, true>(A, g, c, fl, cur, oth, slo, shi, fa.am, &fa);
+            else ens_heun<K, false, TWO, true>(A, g, c, fl, cur, oth, slo, shi, fa.am, &fa);
+            // the wave's key (a wave without a quad has none) and its largest magnitude, by a scan
+            const uint32_t wa = (uint32_t)dpp_all_max_i((int)__float_as_uint(fminf(fa.am, A.clampv)));
+            unsigned tid = threadIdx.x;
+            asm volatile("" : "+v"(tid));  // opaque per step: no lane mask is hoisted and kept in scalars
+            if ((tid & 63) == 0) {
+                if (fa.mw > -__builtin_inff()) atomicMax(&fk[slot], fa.key);
+                atomicMax(&fw[slot], wa);
+            }
+            __syncthreads();  // the step's last barrier: phi' is in cur, the records are posted
+            const unsigned long long key = fk[slot];
+            const uint32_t kM = __builtin_amdgcn_readfirstlane((uint32_t)(key >> 32));
+            const float M = unord_f32_dev(kM);
+            const float D = __uint_as_float(__builtin_amdgcn_readfirstlane((uint32_t)key));
+            const float Am = __uint_as_float(__builtin_amdgcn_readfirstlane(fw[slot]));
+            const int clr = slot == 0 ? 2 : slot - 1;
+            slot = slot == 2 ? 0 : slot + 1;
+            if (tid == 0) {
+                fk[clr] = 0ull;
+                fw[clr] = 0u;
+                float *rec = F.recs + (size_t)r * 3 * (size_t)F.loops + t;  // M | D | A rows of loops entries
+                rec[0] = M;
+                rec[F.loops] = D;
+                rec[2 * F.loops] = Am;
+            }
+            ++exec;
+            if (Am >= E.clampv) gflag = 1;  // a stage's guarded maximum or the final guard reached the clamp
+            const bool fire = M > sT && D > sV;  // stab_rule (sq_phi4_frames.cpp)
+            sT = M;
+            sV = sV < Am ? Am : sV;
+            if (fire) {
+                fired = t;
+                break;  // the verdict is settled, T and V frozen: the rest of the frame is skipped
+            }
+        }
+        sticky |= gflag;
+        const int stable = (gflag == 0 && fired < 0) ? 1 : 0;
+        if (F.adapt) {  // frame_decide
+            if (stable) {
+                if (cnt > 10) {
+                    cnt = 0;
+                    dtau /= 0.950;
+                }
+                cnt += 1;
+            } else {
+                dtau *= 0.950;
+                cnt = 0;
+            }
+        }
+        const float hf = (float)dtau;  // phi4_base_args
+        A.h = hf;
+        A.sig = (float)(__builtin_sqrt(2.0 * (double)hf) * st.C);
+        A.sigq = (float)(__builtin_sqrt(2.0 * (double)hf) * st.C * kSqrt2Ln2);
+        unsigned tid = threadIdx.x;
+        asm volatile("" : "+v"(tid));  // opaque per frame: what the code below forms from it is not hoisted and kept
+        {
+            // the lane's addresses are formed per frame (q opaque): hoisted, they take 2 K registers for the call
+            float4 *gf = reinterpret_cast<float4 *>(E.field + (size_t)r * (size_t)(4 * g.Q));
+            float4 *cur4 = reinterpret_cast<float4 *>(cur);
+            const int T = blockDim.x;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                int q = (int)tid + j * T;
+                asm volatile("" : "+v"(q));
+                if (fl.get(j) & kEnsValid) {
+                    if (stable) {
+                        gf[q] = c[j];  // the next frame's snapshot
+                    } else {
+                        c[j] = gf[q];
+                        cur4[q] = c[j];  // no wave reads cur here (see above)
+                    }
+                }
+            }
+            if (!stable) __syncthreads();  // block-uniform: every lane decided the frame from the same records
+        }
+        if (tid == 0) {
+            F.stable[(size_t)f * gridDim.x + (size_t)r] = stable;
+            F.dtau[(size_t)f * gridDim.x + (size_t)r] = dtau;
+        }
+        if (E.series != nullptr) {
+            double sm[4];
+            float mx;
+            uint32_t fu[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) fu[j] = fl.get(j);
+            ens_sums<K>(g, c, fu, cur, sm, mx);
+            ens_fold(sm, mx, reinterpret_cast<double *>(sb), E.series + 4 * ((size_t)f * gridDim.x + (size_t)r), false,
+                     tid);
+        }
+        if constexpr (PC) {
+            if (stable)  // block-uniform
+                ens_pcorr_measure(g, E, r, cur, reinterpret_cast<double *>(sb + kPhi4EnsFrameScratchBytes),
+                                  ens_pcorr_args(ca...), tid);
+        } else if constexpr (CORR) {
+            if (stable) {
+                const Phi4EnsCorrArgs C = ens_corr_args(ca...);
+                ens_corr<true>(g, E.Lz, cur, reinterpret_cast<double *>(sb + kPhi4EnsFrameScratchBytes),
+                               C.G + (size_t)r * (size_t)(E.Lz / 2 + 1), C.S1 + r, C.nmeas + r, nullptr, tid);
+            }
+        }
+    }
+    if (threadIdx.x == 0) {
+        Phi4EnsFrameState o = st;
+        o.dtau = dtau;
+        o.T = sT;
+        o.V = sV;
+        o.init = 1;
+        o.cnt = cnt;
+        o.fired = fired;
+        o.flag = gflag;
+        o.exec = exec;
+        F.st[r] = o;
+        if (sticky) E.flags[r] = 1;
+    }
+}
+
 template <int K>
 __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_moments_kernel(const Phi4EnsArgs E, const int first,
                                                                              double *out) {
@@ -1169,6 +1456,43 @@ hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, 
     const void *fn = p   ? ens_heun_fn<Phi4EnsPCorrArgs>(sh.K)
                      : c ? ens_heun_fn<Phi4EnsCorrArgs>(sh.K)
                          : ens_heun_fn<>(sh.K);
+    hipError_t e = ens_lds_attr(fn, bytes);
+    if (e != hipSuccess) return e;
+    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+}
+
+namespace {
+template <bool TWO, typename... CA>
+const void *ens_heun_frames_fn(int K) {
+    return K == 1   ? (const void *)&phi4_ens_heun_frames_kernel<1, TWO, CA...>
+           : K == 2 ? (const void *)&phi4_ens_heun_frames_kernel<2, TWO, CA...>
+           : K == 4 ? (const void *)&phi4_ens_heun_frames_kernel<4, TWO, CA...>
+                    : (const void *)&phi4_ens_heun_frames_kernel<8, TWO, CA...>;
+}
+}  // namespace
+
+hipError_t phi4_ens_heun_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs *c,
+                                       const Phi4EnsPCorrArgs *p, int nrep, hipStream_t s) {
+    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
+        f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr || (c != nullptr && p != nullptr))
+        return hipErrorInvalidValue;
+    if (c != nullptr && (c->G == nullptr || c->S1 == nullptr || c->nmeas == nullptr)) return hipErrorInvalidValue;
+    if (p != nullptr && !ens_pcorr_ok(*p, true)) return hipErrorInvalidValue;
+    // the frames launches' layouts, each by its own rule
+    const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, (c || p) ? a.Lz : 0);
+    if (p != nullptr && !sh.pc_ok) return hipErrorInvalidValue;
+    const bool two = p ? sh.pc_fr_two : c ? sh.co_fr_two : sh.fr_two;
+    const int bytes = p ? sh.pc_fr_lds_bytes : c ? sh.co_fr_lds_bytes : sh.fr_lds_bytes;
+    Phi4EnsArgs q = a;
+    Phi4EnsFrameArgs fq = f;
+    Phi4EnsCorrArgs cq = c ? *c : Phi4EnsCorrArgs{};
+    Phi4EnsPCorrArgs pq = p ? *p : Phi4EnsPCorrArgs{};
+    void *args[] = {&q, &fq, p ? (void *)&pq : (void *)&cq};  // the plain instances take the first two
+    const void *fn = p   ? (two ? ens_heun_frames_fn<true, Phi4EnsPCorrArgs>(sh.K)
+                                : ens_heun_frames_fn<false, Phi4EnsPCorrArgs>(sh.K))
+                     : c ? (two ? ens_heun_frames_fn<true, Phi4EnsCorrArgs>(sh.K)
+                                : ens_heun_frames_fn<false, Phi4EnsCorrArgs>(sh.K))
+                         : (two ? ens_heun_frames_fn<true>(sh.K) : ens_heun_frames_fn<false>(sh.K));
     hipError_t e = ens_lds_attr(fn, bytes);
     if (e != hipSuccess) return e;
     return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);

@@ -699,14 +699,23 @@ class Phi4Ensemble:
         _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
         return ser
 
-    def run_frames(self, n, measure=False, correlate=False, momenta=False):
+    def run_frames(self, n, measure=False, correlate=False, momenta=False, scheme="euler"):
         """n frames of every replica in one launch: (stable (n, R) bool, dtau
         (n, R) after each frame), and with `measure` the (n, R, 4) sums S1, S2,
         S4, NN of each replica's field after the frame's verdict (the frame's
         start field again after a rollback).  `correlate`: one correlator
         measurement of the adopted field after every stable frame of a replica
         (a rolled-back frame measures nothing); the return values are unchanged.
-        `momenta`: likewise one measurement of the momentum-projected correlators."""
+        `momenta`: likewise one measurement of the momentum-projected correlators.
+
+        scheme: "euler" (the default) or "heun": every step of the frame is the
+        Heun step of `step(scheme="heun")` (sq_phi4_ens_run_frames_heun), the
+        stability record taken of φ' against the step's input; the rule, the
+        rollback, the controller and the measurements are the same, and T, V,
+        Δτ and the counters are shared with the Euler frames.  Calls of either
+        scheme, and raw steps, may alternate."""
+        if scheme not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n = int(n)
         st = np.zeros((max(n, 0), self.R), dtype=np.int32)
         dt = np.zeros((max(n, 0), self.R))
@@ -714,15 +723,28 @@ class Phi4Ensemble:
         fn, extra = ("sq_phi4_ens_run_frames_corr" if correlate else "sq_phi4_ens_run_frames"), ()
         if momenta:
             fn, extra = "sq_phi4_ens_run_frames_pcorr", (1 if correlate else 0,)
+        if scheme == "heun":
+            fn, extra = "sq_phi4_ens_run_frames_heun", ((1 if correlate else 0) | (2 if momenta else 0),)
         _lib.call(fn, self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
                   None if ser is None else _dptr(ser), *extra)
         if n > 0:
             self._frames_run = True
         return (st != 0, dt) if ser is None else (st != 0, dt, ser)
 
-    def run_frame(self):
+    def run_frame(self, scheme="euler"):
         """One frame of every replica; (R,) bool: stable."""
-        return self.run_frames(1)[0][0]
+        return self.run_frames(1, scheme=scheme)[0][0]
+
+    @staticmethod
+    def heun_frames_shape_info(shape):
+        """The Heun frames launch for a lattice of `shape`
+        (sq_phi4_ens_heun_frames_shape_info; no device needed): {"images" /
+        "lds_bytes" of the plain launch, "measure_mask": bit m set when the
+        shape runs correlate / momenta = bit 0 / bit 1 of m}."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 4)()
+        _lib.call("sq_phi4_ens_heun_frames_shape_info", dims, out)
+        return {"images": int(out[0]), "lds_bytes": int(out[1]), "measure_mask": int(out[2])}
 
     def stability(self, first=0, count=None, n=None):
         """The stability rule's state per replica: {"T", "V", "fired" (step of the
