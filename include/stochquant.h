@@ -636,6 +636,96 @@ int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series,
 int sq_phi4_ens_run_frames_heun(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, int measure);
 int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]);
 
+/* Gradient-flow measurements of the phi^4 ensemble: the sums and the
+ * time-slice correlator taken of a smoothed copy of a replica's field, inside
+ * the resident kernel.  ABI 6: symbols added, none changed.
+ *
+ * Flow parameters, set once per handle (sq_phi4_ens_set_flow): a step eps > 0,
+ * 1 .. SQ_PHI4_ENS_MAX_FLOW_LEVELS strictly ascending levels 0 <= n_1 < ... <
+ * n_F <= SQ_PHI4_ENS_MAX_FLOW_STEPS (flow steps), and optionally a flow mass
+ * m2 and coupling lambda shared by all replicas (NULL: replica r flows with
+ * its own m2 / lambda; m2 = lambda = 0 is the lattice heat equation).
+ *
+ * Flow coefficients of replica r, derived on the host with the expressions of
+ * a context's step coefficients: h = (float)eps, m2 = (float)m2, lam6 =
+ * (float)((double)(float)lambda / 6.0), sig = 0.  They are re-derived whenever
+ * sq_phi4_ens_set_params changes what they depend on and are held to the
+ * parameter bound of sq_phi4_ens_create with (clamp, eps, m2, lambda, C = 0):
+ * a sq_phi4_ens_set_flow or sq_phi4_ens_set_params call that would break it
+ * for one replica returns SQ_E_ARG and changes nothing.
+ *
+ * Flowed field at level j: the noise-off site update of sq_phi4_ens_step (the
+ * full guard, the handle's clamp) applied n_j times to a copy of the replica's
+ * current field with those coefficients; no noise is drawn and no counter
+ * advances.  Bit for bit what an ensemble with C = 0, dtau = eps and those m2,
+ * lambda holds after sq_phi4_ens_upload of the field and sq_phi4_ens_step(n_j).
+ * Level 0 is the field itself; the levels are reached in one pass of n_F steps.
+ * A measurement at a level is the existing one of the flowed field: the four
+ * sums of sq_phi4_ens_step's series, and S(z), g(t), s1 of the correlator
+ * above, in their stated orders.
+ *
+ * The flow does not touch the simulation: after any call with it the fields,
+ * the step counters, the guard flags (a clamp hit DURING THE FLOW sets none),
+ * dtau, T and V, and the plain correlator and momentum accumulators are bit
+ * for bit those of the same call without it.
+ *
+ * sq_phi4_ens_set_flow: nlevels = 0 turns the flow off (levels may be NULL).
+ * Every successful call zeroes the flow accumulators of every replica.
+ * sq_phi4_ens_get_flow: *nlevels (required) and, where given, eps, the levels
+ * (room for SQ_PHI4_ENS_MAX_FLOW_LEVELS) and m2 / lambda, NaN for "each
+ * replica's own".
+ * sq_phi4_ens_step_flow: as sq_phi4_ens_step for fields, counters and flags
+ * (Euler steps).  every >= 1 (else SQ_E_ARG); after each every-th step one
+ * measurement per level: the four sums to series[rec][level][replica][4]
+ * (nullable; an incomplete tail measures nothing) and, correlate != 0, one
+ * correlator measurement per level added to the flow accumulators, per replica
+ * and level G[nt] += g, S1 += s1, nmeas += 1, one addition each.  They persist
+ * across calls and are cleared by sq_phi4_ens_fcorr_reset and
+ * sq_phi4_ens_set_flow only.  The plain accumulators of sq_phi4_ens_corr_sums
+ * do NOT advance: level 0 is the unflowed measurement.  No flow set:
+ * SQ_E_STATE.
+ * sq_phi4_ens_flowed: one measurement per level of the STORED fields of the
+ * range, accumulating nothing and leaving the fields alone: sums[count][F][4],
+ * S[count][F][Lz], g[count][F][nt], each nullable.
+ * sq_phi4_ens_flow_field: the stored fields after nsteps flow steps, 0 <=
+ * nsteps <= SQ_PHI4_ENS_MAX_FLOW_STEPS, to phi[count][sites]; eps, m2 and
+ * lambda of sq_phi4_ens_set_flow are used, the levels are not; the stored
+ * fields are untouched.
+ * sq_phi4_ens_fcorr_sums: the raw flow accumulators, G[count][F][nt],
+ * S1[count][F], nmeas[count] (the levels of a replica share their count), each
+ * nullable.  sq_phi4_ens_fcorr_reset zeroes the range's.
+ * sq_phi4_ens_fcorrelator: the rule of sq_phi4_ens_correlator level by level
+ * through the same host code, mean[F][n], err[F][n] (nullable), n <= nt.
+ * sq_phi4_ens_flowed, _flow_field, _fcorr_sums and _fcorrelator without a flow
+ * set: SQ_E_STATE.
+ * sq_phi4_ens_flow_shape_info (no device, no handle; SQ_E_ARG as
+ * sq_phi4_ens_shape_info): out = {LDS images and dynamic LDS bytes of
+ * sq_phi4_ens_step_flow without the correlator (the plain step launch's),
+ * the same two with it (the correlator step launch's), the LDS bytes of the
+ * sq_phi4_ens_flowed launch, where the un-flowed field waits during a flow
+ * inside the step kernel (0 = registers, 1 = the replica's row in device
+ * memory)}.
+ *
+ * Out of scope for now: a flow together with the momentum measurements, with
+ * Heun steps, or in frames.  There is no entry point for any of them (the
+ * Python binding refuses them before any library call);
+ * sq_phi4_ens_flowed between calls serves those users. */
+#define SQ_PHI4_ENS_MAX_FLOW_LEVELS 4
+#define SQ_PHI4_ENS_MAX_FLOW_STEPS 4096
+int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels,
+                         const double *m2 /*NULL: each replica's own*/, const double *lambda /*likewise*/);
+int sq_phi4_ens_get_flow(sq_phi4_ens *e, double *eps, int *nlevels, int *levels, double *m2, double *lambda);
+int sq_phi4_ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series /*[nsteps/every][F][R][4]*/,
+                          int correlate);
+int sq_phi4_ens_flowed(sq_phi4_ens *e, int first, int count, double *sums /*[count][F][4]*/,
+                       double *S /*[count][F][Lz]*/, double *g /*[count][F][nt]*/);
+int sq_phi4_ens_flow_field(sq_phi4_ens *e, int first, int count, int nsteps, float *phi /*[count][sites]*/);
+int sq_phi4_ens_fcorr_sums(sq_phi4_ens *e, int first, int count, double *G /*[count][F][nt]*/,
+                           double *S1 /*[count][F]*/, long long *nmeas /*[count]*/);
+int sq_phi4_ens_fcorr_reset(sq_phi4_ens *e, int first, int count);
+int sq_phi4_ens_fcorrelator(sq_phi4_ens *e, int connected, double *mean /*[F][n]*/, double *err, int n, int *used);
+int sq_phi4_ens_flow_shape_info(const int dims[3], int out[6]);
+
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */
 int sq_comm_unique_id(unsigned char out[128]);

@@ -210,8 +210,20 @@ SIGNATURES = {
     "sq_phi4_ens_pcorr_shape_info": (ctypes.c_int, [_I, _I]),
     "sq_phi4_ens_run_frames_heun": (ctypes.c_int, [_P, ctypes.c_int, _I, _D, _D, ctypes.c_int]),
     "sq_phi4_ens_heun_frames_shape_info": (ctypes.c_int, [_I, _I]),
+    "sq_phi4_ens_set_flow": (ctypes.c_int, [_P, ctypes.c_double, ctypes.c_int, _I, _D, _D]),
+    "sq_phi4_ens_get_flow": (ctypes.c_int, [_P, _D, _I, _I, _D, _D]),
+    "sq_phi4_ens_step_flow": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int]),
+    "sq_phi4_ens_flowed": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D, _D]),
+    "sq_phi4_ens_flow_field": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _F]),
+    "sq_phi4_ens_fcorr_sums": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, _D,
+                                              ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ens_fcorr_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_fcorrelator": (ctypes.c_int, [_P, ctypes.c_int, _D, _D, ctypes.c_int, _I]),
+    "sq_phi4_ens_flow_shape_info": (ctypes.c_int, [_I, _I]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
+SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4
+SQ_PHI4_ENS_MAX_FLOW_STEPS = 4096
 
 _lib = None
 

@@ -51,6 +51,17 @@ struct sq_phi4_ens {
     size_t pG_cap = 0;                   // ... in momenta
     double *ptmp = nullptr;              // sq_phi4_ens_pslices' device buffer: [count][pM][Lz][2] then [count][pM][nt]
     size_t ptmp_cap = 0;                 // ... in doubles
+    int fF = 0;                          // flow levels set (sq_phi4_ens_set_flow), 0: no flow
+    int flev[SQ_PHI4_ENS_MAX_FLOW_LEVELS] = {};  // ... strictly ascending flow steps
+    double feps = 0.0, fm2 = NAN, flam = NAN;    // flow step; the flow's m², λ (NaN: each replica's own)
+    sq::Phi4EnsFlowRec *frec = nullptr;  // [R] flow coefficients (first set_flow on)
+    bool frec_dirty = true;              // ... are behind rep[] / the flow parameters
+    double *fG = nullptr;                // [R][fF][nt] flow accumulators: zeroed by set_flow and
+    double *fS1 = nullptr;               // [R][fF]     sq_phi4_ens_fcorr_reset only
+    long long *fN = nullptr;             // [R][fF]
+    size_t fG_cap = 0;                   // ... in levels
+    double *ftmp = nullptr;              // sq_phi4_ens_flowed's / _flow_field's device buffer
+    size_t ftmp_cap = 0;                 // ... in bytes
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -145,6 +156,15 @@ void release_phi4_ens(sq_phi4_ens *e) {
     (void)hipFree(e->pG);
     (void)hipFree(e->pN);
     (void)hipFree(e->ptmp);
+    (void)hipFree(e->frec);
+    (void)hipFree(e->fG);
+    (void)hipFree(e->fS1);
+    (void)hipFree(e->fN);
+    (void)hipFree(e->ftmp);
+    e->frec = nullptr;
+    e->fG = e->fS1 = e->ftmp = nullptr;
+    e->fN = nullptr;
+    e->fG_cap = e->ftmp_cap = 0;
     e->ptab = e->pG = e->ptmp = nullptr;
     e->pN = nullptr;
     e->pG_cap = e->ptmp_cap = 0;
@@ -356,6 +376,11 @@ int sq_phi4_ens_set_params(sq_phi4_ens *e, int first, int count, const double *d
         if (!ens_params_ok(e->p.clamp, dtau ? dtau[r] : o.dtau, m2 ? m2[r] : o.m2, lambda ? lambda[r] : o.lambda,
                            C ? C[r] : o.C))
             return fail(SQ_E_ARG, "PHI4 parameters must be finite with dtau > 0 and dtau * drift(clamp) < 1e30");
+        // the replica's flow coefficients follow its m² and λ where the flow has none of its own
+        if (e->fF > 0 && !ens_params_ok(e->p.clamp, e->feps, std::isnan(e->fm2) ? (m2 ? m2[r] : o.m2) : e->fm2,
+                                        std::isnan(e->flam) ? (lambda ? lambda[r] : o.lambda) : e->flam, 0.0))
+            return fail(SQ_E_ARG, "the parameters would make the replica's flow coefficients illegal "
+                                  "(sq_phi4_ens_set_flow)");
     }
     for (int r = 0; r < count; ++r) {
         sq_phi4_ens::Rep &o = e->rep[(size_t)(first + r)];
@@ -365,6 +390,7 @@ int sq_phi4_ens_set_params(sq_phi4_ens *e, int first, int count, const double *d
         if (C) o.C = C[r];
     }
     if (count && (dtau || m2 || lambda || C)) e->rec_dirty = true;
+    if (count && (m2 || lambda)) e->frec_dirty = true;
     return SQ_OK;
 }
 
@@ -863,6 +889,262 @@ int sq_phi4_ens_flags(sq_phi4_ens *e, int first, int count, int *flags, int clea
     if (flags) SQ_HIP(hipMemcpy(flags, e->flags + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
     if (clear) SQ_HIP(hipMemset(e->flags + first, 0, sizeof(int) * (size_t)count));
     if (clear) SQ_HIP(hipDeviceSynchronize());  // the memset ran on the null stream
+    return SQ_OK;
+}
+
+}  // extern "C"
+
+// ---- gradient-flow measurements (sq_phi4_ens_flow.hip) ----
+namespace {
+
+// Replica r's flow coefficients: phi4_base_args' expressions of (eps, m², λ), sig = 0.
+sq::Phi4EnsFlowRec ens_flow_rec(const sq_phi4_ens *e, const sq_phi4_ens::Rep &r) {
+    sq::Phi4EnsFlowRec d{};
+    d.h = (float)e->feps;
+    d.m2 = (float)(std::isnan(e->fm2) ? r.m2 : e->fm2);
+    d.lam6 = (float)((double)(float)(std::isnan(e->flam) ? r.lambda : e->flam) / 6.0);
+    return d;
+}
+
+sq::Phi4EnsFlowArgs ens_flow_args(const sq_phi4_ens *e) {
+    sq::Phi4EnsFlowArgs w{};
+    w.rec = e->frec;
+    w.nlev = e->fF;
+    for (int l = 0; l < e->fF; ++l) w.lev[l] = e->flev[l];
+    w.G = e->fG;
+    w.S1 = e->fS1;
+    w.nmeas = e->fN;
+    return w;
+}
+
+// Bring the device's flow records up to rep[] and the flow parameters (the stream is idle).
+int ens_sync_flow(sq_phi4_ens *e) {
+    if (e->frec && !e->frec_dirty) return SQ_OK;
+    if (!e->frec) SQ_HIP(hipMalloc(&e->frec, sizeof(sq::Phi4EnsFlowRec) * (size_t)e->R));
+    std::vector<sq::Phi4EnsFlowRec> h((size_t)e->R);
+    for (int r = 0; r < e->R; ++r) h[(size_t)r] = ens_flow_rec(e, e->rep[(size_t)r]);
+    SQ_HIP(hipMemcpy(e->frec, h.data(), sizeof(sq::Phi4EnsFlowRec) * h.size(), hipMemcpyHostToDevice));
+    e->frec_dirty = false;
+    return SQ_OK;
+}
+
+int ens_flow_tmp(sq_phi4_ens *e, size_t bytes) {
+    if (bytes <= e->ftmp_cap) return SQ_OK;
+    (void)hipFree(e->ftmp);
+    e->ftmp = nullptr;
+    e->ftmp_cap = 0;
+    SQ_HIP(hipMalloc(&e->ftmp, bytes));
+    e->ftmp_cap = bytes;
+    return SQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels, const double *m2,
+                         const double *lambda) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nlevels < 0 || nlevels > SQ_PHI4_ENS_MAX_FLOW_LEVELS)
+        return fail(SQ_E_ARG, "0 <= nlevels <= SQ_PHI4_ENS_MAX_FLOW_LEVELS flow levels");
+    DeviceGuard g(e->dev);
+    const size_t R = (size_t)e->R, nt = (size_t)e->nt, F = (size_t)nlevels;
+    if (nlevels > 0) {
+        if (!levels) return fail(SQ_E_ARG, "null argument");
+        for (int l = 0; l < nlevels; ++l)
+            if (levels[l] < (l ? levels[l - 1] + 1 : 0) || levels[l] > SQ_PHI4_ENS_MAX_FLOW_STEPS)
+                return fail(SQ_E_ARG, "flow levels must ascend strictly within [0, SQ_PHI4_ENS_MAX_FLOW_STEPS]");
+        const double fm2 = m2 ? *m2 : NAN, flam = lambda ? *lambda : NAN;
+        if ((m2 && !std::isfinite(fm2)) || (lambda && !std::isfinite(flam)))
+            return fail(SQ_E_ARG, "the flow's m2 and lambda must be finite");
+        for (const auto &r : e->rep)  // every replica's flow coefficients or none
+            if (!ens_params_ok(e->p.clamp, eps, m2 ? fm2 : r.m2, lambda ? flam : r.lambda, 0.0))
+                return fail(SQ_E_ARG, "flow parameters must be finite with eps > 0 and eps * drift(clamp) < 1e30");
+        if (F > e->fG_cap) {
+            double *G = nullptr, *S1 = nullptr;
+            long long *N = nullptr;
+            if (hipMalloc(&G, sizeof(double) * R * F * nt) != hipSuccess ||
+                hipMalloc(&S1, sizeof(double) * R * F) != hipSuccess ||
+                hipMalloc(&N, sizeof(long long) * R * F) != hipSuccess) {
+                (void)hipFree(G);
+                (void)hipFree(S1);
+                (void)hipFree(N);
+                return fail(SQ_E_HIP, "hipMalloc of the flow accumulators failed");
+            }
+            (void)hipFree(e->fG);
+            (void)hipFree(e->fS1);
+            (void)hipFree(e->fN);
+            e->fG = G;
+            e->fS1 = S1;
+            e->fN = N;
+            e->fG_cap = F;
+        }
+        e->feps = eps;
+        e->fm2 = fm2;
+        e->flam = flam;
+        for (int l = 0; l < nlevels; ++l) e->flev[l] = levels[l];
+    }
+    e->fF = nlevels;  // the accumulators' layout is [R][F][...] from here on: all of them start over
+    e->frec_dirty = true;
+    if (F > 0) {
+        SQ_HIP(hipMemsetAsync(e->fG, 0, sizeof(double) * R * F * nt, e->stream));
+        SQ_HIP(hipMemsetAsync(e->fS1, 0, sizeof(double) * R * F, e->stream));
+        SQ_HIP(hipMemsetAsync(e->fN, 0, sizeof(long long) * R * F, e->stream));
+        SQ_HIP(hipStreamSynchronize(e->stream));
+    }
+    return SQ_OK;
+}
+
+int sq_phi4_ens_get_flow(sq_phi4_ens *e, double *eps, int *nlevels, int *levels, double *m2, double *lambda) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (!nlevels) return fail(SQ_E_ARG, "null argument");
+    *nlevels = e->fF;
+    if (eps) *eps = e->fF ? e->feps : 0.0;
+    if (levels)
+        for (int l = 0; l < e->fF; ++l) levels[l] = e->flev[l];
+    if (m2) *m2 = e->fF ? e->fm2 : NAN;
+    if (lambda) *lambda = e->fF ? e->flam : NAN;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (every < 1) return fail(SQ_E_ARG, "a flow measurement needs every >= 1");
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    if (nsteps == 0) return SQ_OK;
+    if (!series && !correlate) return ens_step(e, nsteps, 0, nullptr, false);  // nothing to measure
+    DeviceGuard g(e->dev);
+    int rc = ens_sync_recs(e);
+    if (!rc) rc = ens_sync_flow(e);
+    if (rc) return rc;
+    const size_t nrec = series ? (size_t)(nsteps / every) : 0;
+    const size_t nd = nrec * (size_t)e->fF * (size_t)e->R * 4;
+    if (nd > e->series_cap) {  // pinned, written by the kernel (ens_step)
+        (void)hipHostFree(e->series);
+        e->series = nullptr;
+        e->series_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
+        e->series_cap = nd;
+    }
+    if (!nd && !correlate) return ens_step(e, nsteps, 0, nullptr, false);  // an incomplete tail only
+    sq::Phi4EnsArgs a = ens_args(e);
+    a.nsteps = nsteps;
+    a.every = every;
+    a.series = nd ? e->series : nullptr;
+    SQ_HIP(sq::phi4_ens_step_flow_launch(a, ens_flow_args(e), correlate != 0, e->R, e->stream));
+    e->launches++;
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    e->adv += (unsigned long long)nsteps;
+    for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
+    e->steps_total += (long long)nsteps * e->R;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_flowed(sq_phi4_ens *e, int first, int count, double *sums, double *S, double *gt) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    if (count == 0 || (!sums && !S && !gt)) return SQ_OK;
+    DeviceGuard dg(e->dev);
+    rc = ens_sync_flow(e);
+    if (rc) return rc;
+    const size_t n = (size_t)count * (size_t)e->fF, Lz = (size_t)e->Lz, nt = (size_t)e->nt;
+    rc = ens_flow_tmp(e, sizeof(double) * n * (4 + Lz + nt));
+    if (rc) return rc;
+    double *dsum = e->ftmp, *dS = dsum + 4 * n, *dg_ = dS + n * Lz;
+    SQ_HIP(sq::phi4_ens_flowed_launch(ens_args(e), ens_flow_args(e), first, count, dsum, dS, dg_, e->stream));
+    if (sums) SQ_HIP(hipMemcpyAsync(sums, dsum, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, e->stream));
+    if (S) SQ_HIP(hipMemcpyAsync(S, dS, sizeof(double) * n * Lz, hipMemcpyDeviceToHost, e->stream));
+    if (gt) SQ_HIP(hipMemcpyAsync(gt, dg_, sizeof(double) * n * nt, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_flow_field(sq_phi4_ens *e, int first, int count, int nsteps, float *phi) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (nsteps < 0 || nsteps > SQ_PHI4_ENS_MAX_FLOW_STEPS)
+        return fail(SQ_E_ARG, "0 <= nsteps <= SQ_PHI4_ENS_MAX_FLOW_STEPS flow steps");
+    if (!phi) return fail(SQ_E_ARG, "null argument");
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    if (count == 0) return SQ_OK;
+    DeviceGuard dg(e->dev);
+    rc = ens_sync_flow(e);
+    if (rc) return rc;
+    const size_t bytes = sizeof(float) * (size_t)count * e->sites;
+    rc = ens_flow_tmp(e, bytes);
+    if (rc) return rc;
+    float *out = reinterpret_cast<float *>(e->ftmp);
+    SQ_HIP(sq::phi4_ens_flow_field_launch(ens_args(e), ens_flow_args(e), first, count, nsteps, out, e->stream));
+    SQ_HIP(hipMemcpyAsync(phi, out, bytes, hipMemcpyDeviceToHost, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_fcorr_sums(sq_phi4_ens *e, int first, int count, double *G, double *S1, long long *nmeas) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t F = (size_t)e->fF, nt = (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    if (G) SQ_HIP(hipMemcpy(G, e->fG + f * F * nt, sizeof(double) * n * F * nt, hipMemcpyDeviceToHost));
+    if (S1) SQ_HIP(hipMemcpy(S1, e->fS1 + f * F, sizeof(double) * n * F, hipMemcpyDeviceToHost));
+    if (nmeas) {  // every level of a replica has the same count: the first one's
+        std::vector<long long> N(n * F);
+        SQ_HIP(hipMemcpy(N.data(), e->fN + f * F, sizeof(long long) * n * F, hipMemcpyDeviceToHost));
+        for (size_t r = 0; r < n; ++r) nmeas[r] = N[r * F];
+    }
+    return SQ_OK;
+}
+
+int sq_phi4_ens_fcorr_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0 || e->fF == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    const size_t F = (size_t)e->fF, nt = (size_t)e->nt, n = (size_t)count, f = (size_t)first;
+    SQ_HIP(hipMemsetAsync(e->fG + f * F * nt, 0, sizeof(double) * n * F * nt, e->stream));
+    SQ_HIP(hipMemsetAsync(e->fS1 + f * F, 0, sizeof(double) * n * F, e->stream));
+    SQ_HIP(hipMemsetAsync(e->fN + f * F, 0, sizeof(long long) * n * F, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_fcorrelator(sq_phi4_ens *e, int connected, double *mean, double *err, int n, int *used) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (n < 0 || n > e->nt) return fail(SQ_E_ARG, "n must lie in [0, Lz / 2 + 1]");
+    if (!mean && n > 0) return fail(SQ_E_ARG, "null argument");
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    const size_t R = (size_t)e->R, nt = (size_t)e->nt, F = (size_t)e->fF;
+    std::vector<double> G(R * F * nt), S1(R * F), s1(R);
+    std::vector<long long> N(R);
+    int rc = sq_phi4_ens_fcorr_sums(e, 0, e->R, G.data(), S1.data(), N.data());
+    if (rc) return rc;
+    int u = 0;
+    for (size_t r = 0; r < R; ++r) u += N[r] > 0 ? 1 : 0;
+    if (used) *used = u;
+    if (u == 0) return fail(SQ_E_STATE, "no replica has a flow correlator measurement");
+    for (size_t l = 0; l < F; ++l) {  // sq_phi4_ens_correlator's rule, level by level
+        for (size_t r = 0; r < R; ++r) s1[r] = S1[r * F + l];
+        ens_replica_stats(e, G.data() + l * nt, F * nt, connected ? s1.data() : nullptr, N.data(), u, n,
+                          mean + l * (size_t)n, err ? err + l * (size_t)n : nullptr);
+    }
+    return SQ_OK;
+}
+
+int sq_phi4_ens_flow_shape_info(const int dims[3], int out[6]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsFlowShape s = sq::phi4_ens_flow_shape(dims[0] * dims[1] * dims[2], dims[2]);
+    out[0] = s.two ? 2 : 1;
+    out[1] = s.lds_bytes;
+    out[2] = s.co_two ? 2 : 1;
+    out[3] = s.co_lds_bytes;
+    out[4] = s.fl_lds_bytes;
+    out[5] = s.stash;
     return SQ_OK;
 }
 

@@ -156,6 +156,59 @@ hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, 
 // rules are those of the three frames launches; the image count selects the instance.
 hipError_t phi4_ens_heun_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs *c,
                                        const Phi4EnsPCorrArgs *p, int nrep, hipStream_t s);
+// ---- gradient-flow measurements (sq_phi4_ens_flow.hip) ----
+constexpr int kPhi4EnsMaxFlowLevels = 4;    // SQ_PHI4_ENS_MAX_FLOW_LEVELS
+constexpr int kPhi4EnsMaxFlowSteps = 4096;  // SQ_PHI4_ENS_MAX_FLOW_STEPS
+
+// One replica's flow coefficients: phi4_base_args' expressions of the flow step, its m² and λ; sig = 0.
+struct Phi4EnsFlowRec {
+    float h, m2, lam6, pad;
+};
+
+// The flow of a launch: nlev strictly ascending levels (flow steps), lev[nlev - 1] <= kPhi4EnsMaxFlowSteps, and
+// the per-replica, per-level accumulators of the step launch's correlator measurements (nullable without them):
+// G[r][l][t] += g(t), S1[r][l] += s1, nmeas[r][l] += 1.
+struct Phi4EnsFlowArgs {
+    const Phi4EnsFlowRec *rec;  // [R]
+    int nlev;
+    int lev[kPhi4EnsMaxFlowLevels];
+    double *G;          // [R][nlev][nt]
+    double *S1;         // [R][nlev]
+    long long *nmeas;   // [R][nlev]
+};
+
+// What the flow launches ask for, from phi4_ens_shape: the step launch keeps the plain launch's layout without
+// the correlator and the correlator launch's with it, the flowed launch takes the latter, the flow-field launch
+// the former.  stash: where the lane's quads wait during a flow inside the step kernel, 0 registers, 1 the
+// replica's row of the field in device memory (K = 8: no 32 registers to spare).
+struct Phi4EnsFlowShape {
+    int K, T;
+    bool two;
+    int lds_bytes;
+    bool co_two;
+    int co_lds_bytes;
+    bool fl_two;       // the flowed launch
+    int fl_lds_bytes;
+    int stash;
+};
+Phi4EnsFlowShape phi4_ens_flow_shape(int sites, int Lz);
+
+// phi4_ens_step_launch with a flow measurement after each every-th step (a.every >= 1): the lane's quads put
+// aside, w.lev[nlev - 1] steps of ens_step<K, false> with the replica's flow coefficients on the on-chip copy,
+// at each level the four sums to a.series ([nsteps / every][nlev][R][4], nullable) and, corr, one ens_corr
+// measurement into w's accumulators; then the quads and the image restored.  Fields, counters and flags are those
+// of phi4_ens_step_launch; a.series == nullptr && !corr measures nothing and is hipErrorInvalidValue.
+hipError_t phi4_ens_step_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, bool corr, int nrep,
+                                     hipStream_t s);
+// One measurement per level of the stored fields of replicas first .. first + count, which are not written:
+// sums[r][l][4], S[r][l][Lz], g[r][l][nt] (device memory, all non-null).  w.G, w.S1, w.nmeas are not used.
+hipError_t phi4_ens_flowed_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, int first, int count, double *sums,
+                                  double *S, double *g, hipStream_t s);
+// The stored fields of replicas first .. first + count after nsteps flow steps to out[r][sites] (device memory);
+// the stored fields are not written.  Only w.rec is used.
+hipError_t phi4_ens_flow_field_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, int first, int count,
+                                      int nsteps, float *out, hipStream_t s);
+
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

@@ -1267,6 +1267,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_pslices_kernel(cons
                      AB + (size_t)blockIdx.x * (size_t)(P.M * 2 * E.Lz));
 }
 
+#ifndef SQ_PHI4_ENS_KERNELS_ONLY  // sq_phi4_ens_flow.hip includes the device functions and templates, not what follows
 // phi4_init_kernel's field for every replica (blockIdx.y) from its own key.
 __global__ __launch_bounds__(256) void phi4_ens_init_kernel(const Phi4EnsArgs E, const float amp) {
     const int r = blockIdx.y;
@@ -1278,6 +1279,8 @@ __global__ __launch_bounds__(256) void phi4_ens_init_kernel(const Phi4EnsArgs E,
         gf[q] = make_float4(amp * n.a, amp * n.b, amp * n.c, amp * n.d);
     }
 }
+
+#endif  // SQ_PHI4_ENS_KERNELS_ONLY
 
 hipError_t ens_lds_attr(const void *fn, int bytes) {
     // above the default dynamic-LDS ceiling the function needs the attribute (once per instance and device;
@@ -1294,6 +1297,7 @@ bool ens_shape_ok(const Phi4EnsArgs &a) {
 
 }  // namespace
 
+#ifndef SQ_PHI4_ENS_KERNELS_ONLY  // the launchers below belong to this translation unit alone
 Phi4EnsShape phi4_ens_shape(int sites, int Lz) {
     Phi4EnsShape s;
     const int Q = sites / 4;
@@ -1585,5 +1589,6 @@ hipError_t phi4_ens_init_launch(const Phi4EnsArgs &a, int nrep, float amp, hipSt
     }
     return hipSuccess;
 }
+#endif  // SQ_PHI4_ENS_KERNELS_ONLY
 
 }  // namespace sq

@@ -14,6 +14,8 @@ Everything computes on the MI355X through libstochquant.so; nothing here has a
 CPU path.
 """
 import ctypes
+import functools
+import inspect
 import io
 import os
 import subprocess
@@ -512,6 +514,30 @@ class Phi4Lattice(_Ctx):
         _lib.call("sq_p2p_connect", self._h, buf, len(blobs))
 
 
+def _accepts_flow(step):
+    """`Phi4Ensemble.step` with the keyword-only `flow`: flow=True hands the call
+    to `step_flow` after refusing what the flow does not run with.  The
+    positional parameters, their order and their defaults stay those of `step`
+    itself, which is what introspection reports (functools.wraps)."""
+    sig = inspect.signature(step)
+
+    @functools.wraps(step)
+    def wrapper(self, *args, flow=False, **kw):
+        if not flow:
+            return step(self, *args, **kw)
+        a = sig.bind(self, *args, **kw)
+        a.apply_defaults()
+        a = a.arguments
+        if a["scheme"] not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {a['scheme']!r}")
+        if a["momenta"]:
+            raise ValueError("flow=True does not run with momenta=True (use flowed() between calls)")
+        if a["scheme"] == "heun":
+            raise ValueError("flow=True does not run with scheme='heun' (use flowed() between calls)")
+        return self.step_flow(a["n"], a["every"], correlate=a["correlate"])
+    return wrapper
+
+
 class Phi4Ensemble:
     """`replicas` independent periodic φ⁴ lattices of one shape (Lx, Ly, Lz),
     each with its own seed, Δτ, m², λ and C, advanced together: one launch per
@@ -524,7 +550,9 @@ class Phi4Ensemble:
     replica inside the kernel, one launch per call, as `Phi4Lattice.run_frames`
     decides them for one lattice.  Both can measure, in flight, the time-slice
     correlator over z at zero momentum (`correlate`) and at up to eight spatial
-    momenta set with `set_momenta` (`momenta`).
+    momenta set with `set_momenta` (`momenta`).  With `set_flow`, `step` can
+    also flow a copy of every field (the noise-off update, a gradient flow)
+    and measure the smoothed copies at up to four flow levels (`flow`).
 
     dtau, m2, lam and C are scalars or length-R sequences; seeds defaults to
     seed + r."""
@@ -662,6 +690,7 @@ class Phi4Ensemble:
         s = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.uint64), (self.R,)))
         _lib.call("sq_phi4_ens_set_step", self._h, 0, self.R, s.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
 
+    @_accepts_flow
     def step(self, n=1, every=0, correlate=False, momenta=False, scheme="euler"):
         """n steps of every replica in one launch.  every = k > 0: returns the
         (n // k, R, 4) array of S1 = Σφ, S2 = Σφ², S4 = Σφ⁴ and NN = Σ over
@@ -679,7 +708,13 @@ class Phi4Ensemble:
         Euler update at the step's counter, φ' = guard(0.5 (φ + E(E(φ)))), both
         applications with the same noise; the counter advances by one per Heun
         step, and `every`, `correlate` and `momenta` count and measure Heun
-        steps.  Calls of either scheme may alternate."""
+        steps.  Calls of either scheme may alternate.
+
+        The keyword-only flow=True (needs every >= 1 and `set_flow`; Euler steps,
+        no momenta) is `step_flow(n, every, correlate)`: the measurements are
+        taken of flowed copies of the fields, see there.  It is refused with
+        ValueError, before any library call, with every < 1, momenta=True or
+        scheme="heun"."""
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n, every = int(n), int(every)
@@ -697,6 +732,24 @@ class Phi4Ensemble:
             return None
         ser = np.zeros((max(n, 0) // every, self.R, 4))
         _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
+        return ser
+
+    def step_flow(self, n=1, every=1, correlate=False):
+        """n Euler steps of every replica in one launch, as `step`, with a flow
+        measurement after each every-th step (every >= 1, `set_flow` first;
+        sq_phi4_ens_step_flow): the kernel flows a copy of every field and
+        measures at each of the F flow levels.  Returns the (n // every, F, R, 4)
+        array of the flowed fields' sums; `correlate` adds one correlator
+        measurement per level to the FLOW accumulators (`fcorr_sums`,
+        `fcorrelator`), not to the plain ones.  Fields, counters and flags are
+        those of `step(n)`.  `step(n, every=k, flow=True, correlate=...)` is
+        this call."""
+        n, every = int(n), int(every)
+        if every < 1:
+            raise ValueError("a flow measurement needs every >= 1")
+        ser = np.zeros((max(n, 0) // every, self._flow_levels(), self.R, 4))
+        _lib.call("sq_phi4_ens_step_flow", self._h, n, every, _dptr(ser) if ser.size else None,
+                  1 if correlate else 0)
         return ser
 
     def run_frames(self, n, measure=False, correlate=False, momenta=False, scheme="euler"):
@@ -901,6 +954,100 @@ class Phi4Ensemble:
         out = (ctypes.c_int * 6)()
         _lib.call("sq_phi4_ens_pcorr_shape_info", dims, out)
         return dict(zip(("images", "lds_bytes", "frames_images", "frames_lds_bytes", "slices_lds_bytes", "nt"),
+                        (int(v) for v in out)))
+
+    def set_flow(self, eps, levels=(), m2=None, lam=None):
+        """The gradient flow measured by step(flow=True), `flowed` and
+        `flow_field`: flow step eps > 0, up to 4 strictly ascending levels
+        (numbers of flow steps, 0 = the field itself, at most 4096), and
+        optionally the flow's own m² and λ for all replicas (None: each
+        replica's own; 0 and 0: the lattice heat equation).  set_flow(None)
+        turns the flow off.  Zeroes the flow accumulators of every replica;
+        raises, changing nothing, where a replica's flow coefficients would
+        break the parameter bound."""
+        if eps is None:
+            _lib.call("sq_phi4_ens_set_flow", self._h, 0.0, 0, None, None, None)
+            return
+        lv = np.ascontiguousarray(np.asarray(list(levels), dtype=np.int32).reshape(-1))
+        m, l = (None if v is None else ctypes.c_double(float(v)) for v in (m2, lam))
+        _lib.call("sq_phi4_ens_set_flow", self._h, float(eps), lv.shape[0],
+                  lv.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if lv.size else None,
+                  None if m is None else ctypes.byref(m), None if l is None else ctypes.byref(l))
+
+    @property
+    def flow(self):
+        """The flow set: {"eps", "levels" (tuple), "m2", "lam" (None: each replica's own)}, or None."""
+        eps, m, l = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_double(0.0)
+        F = ctypes.c_int(0)
+        lv = (ctypes.c_int * _lib.SQ_PHI4_ENS_MAX_FLOW_LEVELS)()
+        _lib.call("sq_phi4_ens_get_flow", self._h, ctypes.byref(eps), ctypes.byref(F), lv, ctypes.byref(m),
+                  ctypes.byref(l))
+        if F.value == 0:
+            return None
+        return {"eps": eps.value, "levels": tuple(int(v) for v in lv[:F.value]),
+                "m2": None if np.isnan(m.value) else m.value, "lam": None if np.isnan(l.value) else l.value}
+
+    def _flow_levels(self):
+        f = self.flow
+        return len(f["levels"]) if f else 0
+
+    def flowed(self, first=0, count=None):
+        """One measurement per flow level of the current fields, accumulating
+        nothing and leaving the fields alone: (sums (count, F, 4) = S1, S2, S4,
+        NN, S (count, F, Lz) slice sums, g (count, F, nt))."""
+        k, F = self._count(first, count), self._flow_levels()
+        sums = np.zeros((max(k, 0), F, 4))
+        S = np.zeros((max(k, 0), F, self.shape[2]))
+        g = np.zeros((max(k, 0), F, self.nt))
+        _lib.call("sq_phi4_ens_flowed", self._h, int(first), k, _dptr(sums), _dptr(S), _dptr(g))
+        return sums, S, g
+
+    def flow_field(self, nsteps, first=0, count=None):
+        """The current fields after `nsteps` flow steps (0 .. 4096) with the
+        step, m² and λ of `set_flow`: (count, Lz, Ly, Lx); the stored fields are
+        untouched."""
+        k = self._count(first, count)
+        a = np.empty((max(k, 0),) + self.lattice_shape, dtype=np.float32)
+        _lib.call("sq_phi4_ens_flow_field", self._h, int(first), k, int(nsteps), _fptr(a))
+        return a
+
+    def fcorr_sums(self, first=0, count=None):
+        """The raw flow accumulators of replicas first .. first + count: (G
+        (count, F, nt), S1 (count, F), nmeas (count,) int64), per level what
+        `corr_sums` holds for the plain correlator."""
+        k, F = self._count(first, count), self._flow_levels()
+        G = np.zeros((max(k, 0), F, self.nt))
+        S1 = np.zeros((max(k, 0), F))
+        nm = np.zeros(max(k, 0), dtype=np.int64)
+        _lib.call("sq_phi4_ens_fcorr_sums", self._h, int(first), k, _dptr(G), _dptr(S1),
+                  nm.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return G, S1, nm
+
+    def fcorr_reset(self, first=0, count=None):
+        """Zero the flow accumulators of replicas first .. first + count (`set_flow` clears all of them)."""
+        _lib.call("sq_phi4_ens_fcorr_reset", self._h, int(first), self._count(first, count))
+
+    def fcorrelator(self, n=None, connected=True):
+        """(mean (F, n), err (F, n), used): `correlator`'s statistics per flow level."""
+        n, F = (self.nt if n is None else int(n)), self._flow_levels()
+        mean, err = np.zeros((F, max(n, 0))), np.zeros((F, max(n, 0)))
+        used = ctypes.c_int(0)
+        _lib.call("sq_phi4_ens_fcorrelator", self._h, 1 if connected else 0, _dptr(mean), _dptr(err), n,
+                  ctypes.byref(used))
+        return mean, err, used.value
+
+    @staticmethod
+    def flow_shape_info(shape):
+        """The flow launches' LDS layout for a lattice of `shape`
+        (sq_phi4_ens_flow_shape_info; no device needed): {"images" / "lds_bytes"
+        of step(flow=True) without the correlator (the plain step launch's),
+        "corr_images" / "corr_lds_bytes" with it (the correlator step launch's),
+        "flowed_lds_bytes", "stash": where the un-flowed field waits during a
+        flow, 0 = registers, 1 = device memory}."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 6)()
+        _lib.call("sq_phi4_ens_flow_shape_info", dims, out)
+        return dict(zip(("images", "lds_bytes", "corr_images", "corr_lds_bytes", "flowed_lds_bytes", "stash"),
                         (int(v) for v in out)))
 
     def flags(self, clear=False, first=0, count=None):
