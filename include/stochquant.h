@@ -706,10 +706,43 @@ int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]);
  * inside the step kernel (0 = registers, 1 = the replica's row in device
  * memory)}.
  *
- * Out of scope for now: a flow together with the momentum measurements, with
- * Heun steps, or in frames.  There is no entry point for any of them (the
- * Python binding refuses them before any library call);
- * sq_phi4_ens_flowed between calls serves those users. */
+ * sq_phi4_ens_step_flow_heun: sq_phi4_ens_step_flow with every step the Heun
+ * step of sq_phi4_ens_step_heun: one measurement per level after each every-th
+ * Heun step, series[nsteps / every][F][R][4], the same argument rules and early
+ * returns (every < 1: SQ_E_ARG; no flow set: SQ_E_STATE; neither series nor
+ * correlate: the plain Heun call; an incomplete tail measures nothing).
+ * sq_phi4_ens_run_frames_flow: the frames call of `scheme` (SQ_SCHEME_EULER:
+ * sq_phi4_ens_run_frames, SQ_SCHEME_HEUN: sq_phi4_ens_run_frames_heun; another
+ * value: SQ_E_ARG) with the flow measurement behind every frame's verdict.
+ * series (nullable, [nframes][F][R][4]): after EVERY frame the F levels' sums
+ * of the field the replica then holds, the adopted field after a stable frame,
+ * the frame's start field again after a rollback; with level 0 among the
+ * levels that row is bit for bit the series of the frames call itself.
+ * correlate != 0: after every STABLE frame one correlator measurement per
+ * level added to the flow accumulators; a rolled-back frame adds nothing, and
+ * with series == NULL it runs no flow step.  The plain correlator and momentum
+ * accumulators stay at rest.  series == NULL and correlate == 0: the plain
+ * frames call of that scheme.  No flow set: SQ_E_STATE; the other argument
+ * rules are those of sq_phi4_ens_run_frames (loops >= 1, nframes == 0 does
+ * nothing); a refused call changes nothing.  The paragraph "The flow does not
+ * touch the simulation" covers both calls, for frames also stable[], dtau[],
+ * the controller's count and the step records of sq_phi4_ens_stability.
+ * sq_phi4_ens_frames_flow_shape_info (no device, no handle; SQ_E_ARG as
+ * sq_phi4_ens_shape_info): out[0], out[1] = LDS images and dynamic LDS bytes
+ * of sq_phi4_ens_run_frames_flow without the correlator (either scheme: the
+ * frames launch's layout), out[2], out[3] = the same with it (the correlator
+ * frames launch's), out[4] = the images of sq_phi4_ens_step_flow_heun without
+ * the correlator (the plain step launch's layout) | with it << 8, out[5] = its
+ * LDS bytes with the correlator (the correlator step launch's), out[6] = where
+ * the un-flowed field waits (0 = registers, 1 = the replica's row in device
+ * memory): bit 0 Euler frames, bit 1 Heun frames, bit 2 Heun steps, out[7] = a
+ * mask, bit 2 scheme + (correlate != 0) set when sq_phi4_ens_run_frames_flow
+ * runs that combination on the shape (a lacking one is SQ_E_ARG there; every
+ * legal shape has all four).
+ *
+ * Out of scope for now: a flow together with the momentum measurements.  There
+ * is no entry point for it (the Python binding refuses it before any library
+ * call); sq_phi4_ens_flowed between calls serves those users. */
 #define SQ_PHI4_ENS_MAX_FLOW_LEVELS 4
 #define SQ_PHI4_ENS_MAX_FLOW_STEPS 4096
 int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels,
@@ -725,6 +758,12 @@ int sq_phi4_ens_fcorr_sums(sq_phi4_ens *e, int first, int count, double *G /*[co
 int sq_phi4_ens_fcorr_reset(sq_phi4_ens *e, int first, int count);
 int sq_phi4_ens_fcorrelator(sq_phi4_ens *e, int connected, double *mean /*[F][n]*/, double *err, int n, int *used);
 int sq_phi4_ens_flow_shape_info(const int dims[3], int out[6]);
+int sq_phi4_ens_step_flow_heun(sq_phi4_ens *e, int nsteps, int every, double *series /*[nsteps/every][F][R][4]*/,
+                               int correlate);
+int sq_phi4_ens_run_frames_flow(sq_phi4_ens *e, int nframes, int *stable /*[nframes][R]*/,
+                                double *dtau /*[nframes][R]*/, double *series /*[nframes][F][R][4], nullable*/,
+                                int correlate, int scheme /*SQ_SCHEME_EULER or SQ_SCHEME_HEUN*/);
+int sq_phi4_ens_frames_flow_shape_info(const int dims[3], int out[8]);
 
 /* RCCL bootstrap: rank 0 creates the id, the caller distributes it (e.g. via
  * torch.distributed) into sq_params.comm_id of every rank. */

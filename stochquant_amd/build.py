@@ -29,14 +29,16 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = os.environ.get("SQ_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SOURCES = ["sq_phi4.hip", "sq_phi4_run.hip", "sq_qm1d.hip", "sq_qm1d_ens.hip", "sq_qm1d_gs.hip", "sq_phi4_ens.hip",
-                  "sq_phi4_ens_flow.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
+                  "sq_phi4_ens_flow.hip", "sq_phi4_ens_flow_frames.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
 HOST_SOURCES = ["sq_core.cpp", "sq_comm.cpp", "sq_phi4_create.cpp", "sq_phi4_plan.cpp", "sq_phi4_steps.cpp",
                 "sq_phi4_frames.cpp", "sq_phi4_fields.cpp", "sq_qm1d_host.cpp", "sq_ens.cpp", "sq_phi4_ens.cpp",
                 "sq_diag.cpp", "sq_io.cpp"]
-HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h", "sq_qm1d_math.h"]
+HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h", "sq_phi4_ens_flow_dev.h",
+           "sq_qm1d_math.h"]
 # device sources that include another one
 INCLUDES = {"sq_phi4_run.hip": ["sq_phi4.hip"], "sq_phi4_ens.hip": ["sq_phi4.hip"],
-            "sq_phi4_ens_flow.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"]}
+            "sq_phi4_ens_flow.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
+            "sq_phi4_ens_flow_frames.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-Wall",
           "-Wno-unused-function"]
 

@@ -441,7 +441,9 @@ int sq_phi4_ens_step_corr(sq_phi4_ens *e, int nsteps, int every, double *series)
 
 namespace {
 int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr,
-                   bool pcorr = false, bool heun = false);
+                   bool pcorr = false, bool heun = false, bool flow = false);
+int ens_sync_flow(sq_phi4_ens *e);
+sq::Phi4EnsFlowArgs ens_flow_args(const sq_phi4_ens *e);
 }
 
 int sq_phi4_ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series) {
@@ -457,9 +459,10 @@ int sq_phi4_ens_run_frames_corr(sq_phi4_ens *e, int nframes, int *stable, double
 namespace {
 
 // heun: the same call with the Heun frames kernel (sq_phi4_ens_run_frames_heun); one Heun step counts as one
-// step everywhere on the host.
+// step everywhere on the host.  flow (sq_phi4_ens_run_frames_flow; a flow is set, series or corr given, no
+// pcorr): the flow launch of the scheme, series [nframes][F][R][4], corr the flow accumulators'.
 int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, bool corr, bool pcorr,
-                   bool heun) {
+                   bool heun, bool flow) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
     if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
@@ -470,6 +473,7 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
     const int L = e->p.loops;
     const size_t R = (size_t)e->R, n = (size_t)nframes;
     int rc = ens_sync_recs(e);
+    if (!rc && flow) rc = ens_sync_flow(e);
     if (rc) return rc;
     if (!e->frecs) {
         SQ_HIP(hipMalloc(&e->frecs, sizeof(float) * 3 * (size_t)L * R));
@@ -486,7 +490,7 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
         SQ_HIP(hipMalloc(&e->fr_dtau, sizeof(double) * n * R));
         e->fr_cap = n;
     }
-    const size_t nd = series ? n * R * 4 : 0;
+    const size_t nd = series ? n * (flow ? (size_t)e->fF : 1) * R * 4 : 0;
     if (nd > e->series_cap) {  // pinned, written by the kernel (sq_phi4_ens_step)
         (void)hipHostFree(e->series);
         e->series = nullptr;
@@ -510,7 +514,9 @@ int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, doubl
     f.nframes = nframes;
     f.loops = L;
     f.adapt = e->p.adapt_dtau ? 1 : 0;
-    if (heun) {
+    if (flow) {
+        SQ_HIP(sq::phi4_ens_frames_flow_launch(a, f, ens_flow_args(e), corr, heun, e->R, e->stream));
+    } else if (heun) {
         const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
         const sq::Phi4EnsPCorrArgs p = pcorr ? ens_pcorr_args(e, corr) : sq::Phi4EnsPCorrArgs{};
         SQ_HIP(sq::phi4_ens_heun_frames_launch(a, f, (corr && !pcorr) ? &c : nullptr, pcorr ? &p : nullptr, e->R,
@@ -1007,13 +1013,17 @@ int sq_phi4_ens_get_flow(sq_phi4_ens *e, double *eps, int *nlevels, int *levels,
     return SQ_OK;
 }
 
-int sq_phi4_ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate) {
+}  // extern "C"
+
+namespace {
+// sq_phi4_ens_step_flow, and with heun sq_phi4_ens_step_flow_heun: the same call with the Heun kernels.
+int ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate, bool heun) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
     if (every < 1) return fail(SQ_E_ARG, "a flow measurement needs every >= 1");
     if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
     if (nsteps == 0) return SQ_OK;
-    if (!series && !correlate) return ens_step(e, nsteps, 0, nullptr, false);  // nothing to measure
+    if (!series && !correlate) return ens_step(e, nsteps, 0, nullptr, false, false, heun);  // nothing to measure
     DeviceGuard g(e->dev);
     int rc = ens_sync_recs(e);
     if (!rc) rc = ens_sync_flow(e);
@@ -1027,18 +1037,62 @@ int sq_phi4_ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series,
         SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
         e->series_cap = nd;
     }
-    if (!nd && !correlate) return ens_step(e, nsteps, 0, nullptr, false);  // an incomplete tail only
+    if (!nd && !correlate) return ens_step(e, nsteps, 0, nullptr, false, false, heun);  // an incomplete tail only
     sq::Phi4EnsArgs a = ens_args(e);
     a.nsteps = nsteps;
     a.every = every;
     a.series = nd ? e->series : nullptr;
-    SQ_HIP(sq::phi4_ens_step_flow_launch(a, ens_flow_args(e), correlate != 0, e->R, e->stream));
+    if (heun) SQ_HIP(sq::phi4_ens_heun_flow_launch(a, ens_flow_args(e), correlate != 0, e->R, e->stream));
+    else SQ_HIP(sq::phi4_ens_step_flow_launch(a, ens_flow_args(e), correlate != 0, e->R, e->stream));
     e->launches++;
     SQ_HIP(hipStreamSynchronize(e->stream));
     if (nd) memcpy(series, e->series, sizeof(double) * nd);
     e->adv += (unsigned long long)nsteps;
     for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
     e->steps_total += (long long)nsteps * e->R;
+    return SQ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_step_flow(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate) {
+    return ens_step_flow(e, nsteps, every, series, correlate, false);
+}
+
+int sq_phi4_ens_step_flow_heun(sq_phi4_ens *e, int nsteps, int every, double *series, int correlate) {
+    return ens_step_flow(e, nsteps, every, series, correlate, true);
+}
+
+int sq_phi4_ens_run_frames_flow(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, int correlate,
+                                int scheme) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (scheme != SQ_SCHEME_EULER && scheme != SQ_SCHEME_HEUN)
+        return fail(SQ_E_ARG, "scheme must be SQ_SCHEME_EULER or SQ_SCHEME_HEUN");
+    if (nframes < 0) return fail(SQ_E_ARG, "nframes < 0");
+    if (e->p.loops < 1) return fail(SQ_E_ARG, "frames need loops >= 1");
+    if (e->fF == 0) return fail(SQ_E_STATE, "no flow set (sq_phi4_ens_set_flow)");
+    const bool heun = scheme == SQ_SCHEME_HEUN;
+    if (!series && !correlate) return ens_run_frames(e, nframes, stable, dtau, nullptr, false, false, heun);
+    const sq::Phi4EnsFramesFlowShape sh = sq::phi4_ens_frames_flow_shape((int)e->sites, e->Lz);
+    if (!((sh.mask >> (2 * (heun ? 1 : 0) + (correlate ? 1 : 0))) & 1))
+        return fail(SQ_E_ARG, "the lattice shape has no frames-flow launch of this scheme and correlator choice "
+                              "(sq_phi4_ens_frames_flow_shape_info)");
+    return ens_run_frames(e, nframes, stable, dtau, series, correlate != 0, false, heun, true);
+}
+
+int sq_phi4_ens_frames_flow_shape_info(const int dims[3], int out[8]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsFramesFlowShape s = sq::phi4_ens_frames_flow_shape(dims[0] * dims[1] * dims[2], dims[2]);
+    out[0] = s.fr_two ? 2 : 1;
+    out[1] = s.fr_lds_bytes;
+    out[2] = s.co_fr_two ? 2 : 1;
+    out[3] = s.co_fr_lds_bytes;
+    out[4] = (s.hs_two ? 2 : 1) | ((s.co_hs_two ? 2 : 1) << 8);
+    out[5] = s.co_hs_lds_bytes;
+    out[6] = s.fr_stash | (s.hfr_stash << 1) | (s.hs_stash << 2);
+    out[7] = s.mask;
     return SQ_OK;
 }
 

@@ -209,6 +209,39 @@ hipError_t phi4_ens_flowed_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w
 hipError_t phi4_ens_flow_field_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, int first, int count,
                                       int nsteps, float *out, hipStream_t s);
 
+// ---- flow measurements in frames and Heun steps (sq_phi4_ens_flow_frames.hip) ----
+// What those launches ask for, from phi4_ens_shape.  The frames launches of both schemes keep the frames launch's
+// layout without the correlator and the correlator frames launch's with it; the Heun step launch keeps the step
+// launches' as phi4_ens_step_flow_launch does.  *_stash: where the un-flowed field waits, 0 registers, 1 the
+// replica's row of the field in device memory.  mask: bit 2 scheme + corr set when the frames launch of that
+// scheme (0 Euler, 1 Heun) and correlator choice runs on the shape.
+struct Phi4EnsFramesFlowShape {
+    int K, T;
+    bool fr_two;          // the frames launches without the correlator
+    int fr_lds_bytes;
+    bool co_fr_two;       // ... with it
+    int co_fr_lds_bytes;
+    bool hs_two;          // the Heun step launch without the correlator
+    int hs_lds_bytes;
+    bool co_hs_two;       // ... with it
+    int co_hs_lds_bytes;
+    int fr_stash, hfr_stash, hs_stash;  // Euler frames, Heun frames, Heun steps
+    int mask;
+};
+Phi4EnsFramesFlowShape phi4_ens_frames_flow_shape(int sites, int Lz);
+
+// phi4_ens_frames_launch (heun: phi4_ens_heun_frames_launch) with a flow measurement behind every frame's
+// verdict: a.series ([nframes][nlev][R][4], nullable) takes each level's sums of the field the replica then
+// holds, after every frame; corr: one ens_corr measurement per level into w's accumulators after every stable
+// frame.  With a.series == nullptr a rolled-back frame runs no flow step.  The simulation is that of the launch
+// without the flow, bit for bit.  a.series == nullptr && !corr measures nothing and is hipErrorInvalidValue, as
+// is a combination the shape's mask lacks.
+hipError_t phi4_ens_frames_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsFlowArgs &w,
+                                       bool corr, bool heun, int nrep, hipStream_t s);
+// phi4_ens_step_flow_launch with every step the Heun step of phi4_ens_heun_launch.
+hipError_t phi4_ens_heun_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, bool corr, int nrep,
+                                     hipStream_t s);
+
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.

@@ -29,43 +29,18 @@
 // phi4_ens_flowed_kernel and phi4_ens_flow_field_kernel load the stored field,
 // flow, and measure per level / store to a buffer of their own; they never
 // write E.field.
+//
+// The same measurement inside the frames kernels and the Heun step kernel is
+// sq_phi4_ens_flow_frames.hip; what the two files share (ens_flow_args,
+// ens_flow_step, ens_flow_measure, ens_flow_levels_ok) is sq_phi4_ens_flow_dev.h.
 #define SQ_PHI4_ENS_KERNELS_ONLY
 #include "sq_phi4_ens.hip"
+
+#include "sq_phi4_ens_flow_dev.h"  // ens_flow_args, ens_flow_step, ens_flow_measure, ens_flow_levels_ok
 
 namespace sq {
 
 namespace {
-
-__device__ __forceinline__ Phi4StepArgs ens_flow_args(const Phi4EnsFlowRec &fr, float clampv) {
-    Phi4StepArgs A{};
-    A.h = fr.h;
-    A.m2 = fr.m2;
-    A.lam6 = fr.lam6;
-    A.sig = 0.f;
-    A.sigq = 0.f;
-    A.clampv = clampv;
-    return A;
-}
-
-// One flow step: c <- update(c, fc) with the noise off, the result to the other image, behind a barrier.
-template <int K>
-__device__ __forceinline__ void ens_flow_step(const Phi4StepArgs &FA, const EnsGeo &g, float4 (&c)[K],
-                                              const uint32_t (&fl)[K], float *&fc, float *&fo, int two) {
-    const int T = blockDim.x;
-    float fam = 0.f;  // thrown away: a clamp hit during the flow sets no flag
-    ens_step<K, false>(FA, g, c, fl, fc, 0u, 0u, fam);
-    if (!two) __syncthreads();  // one image: every wave has read it
-    {
-        float *x = fc;
-        fc = fo;
-        fo = x;
-    }
-    float4 *fc4 = reinterpret_cast<float4 *>(fc);
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-        if (fl[j] & kEnsValid) fc4[(int)threadIdx.x + j * T] = c[j];
-    __syncthreads();
-}
 
 // two != 0: two LDS images.  CA empty: the plain launch's layout, the sums only (E.series non-null).  CA =
 // {Phi4EnsCorrArgs} (its fields unused: the accumulators are the flow's): the correlator launch's layout, one
@@ -232,13 +207,6 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_flow_field_kernel(c
 #pragma unroll
     for (int j = 0; j < K; ++j)
         if (fl[j] & kEnsValid) of[(int)threadIdx.x + j * T] = c[j];
-}
-
-bool ens_flow_levels_ok(const Phi4EnsFlowArgs &w) {
-    if (w.rec == nullptr || w.nlev < 1 || w.nlev > kPhi4EnsMaxFlowLevels) return false;
-    for (int l = 0; l < w.nlev; ++l)
-        if (w.lev[l] < (l ? w.lev[l - 1] + 1 : 0) || w.lev[l] > kPhi4EnsMaxFlowSteps) return false;
-    return true;
 }
 
 template <typename... CA>

@@ -533,8 +533,31 @@ def _accepts_flow(step):
         if a["momenta"]:
             raise ValueError("flow=True does not run with momenta=True (use flowed() between calls)")
         if a["scheme"] == "heun":
-            raise ValueError("flow=True does not run with scheme='heun' (use flowed() between calls)")
+            raise ValueError("step(flow=True) does not run with scheme='heun' (use step_flow(..., scheme='heun'))")
         return self.step_flow(a["n"], a["every"], correlate=a["correlate"])
+    return wrapper
+
+
+def _frames_accept_flow(run_frames):
+    """`Phi4Ensemble.run_frames` with the keyword-only `flow`, made as
+    `_accepts_flow` makes `step`'s: flow=True hands the call to
+    `run_frames_flow` (`measure` is ignored: the series is always returned)
+    after refusing momenta=True; the signature introspection reports stays
+    that of `run_frames` itself."""
+    sig = inspect.signature(run_frames)
+
+    @functools.wraps(run_frames)
+    def wrapper(self, *args, flow=False, **kw):
+        if not flow:
+            return run_frames(self, *args, **kw)
+        a = sig.bind(self, *args, **kw)
+        a.apply_defaults()
+        a = a.arguments
+        if a["scheme"] not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {a['scheme']!r}")
+        if a["momenta"]:
+            raise ValueError("flow=True does not run with momenta=True (use flowed() between calls)")
+        return self.run_frames_flow(a["n"], correlate=a["correlate"], scheme=a["scheme"])
     return wrapper
 
 
@@ -550,9 +573,10 @@ class Phi4Ensemble:
     replica inside the kernel, one launch per call, as `Phi4Lattice.run_frames`
     decides them for one lattice.  Both can measure, in flight, the time-slice
     correlator over z at zero momentum (`correlate`) and at up to eight spatial
-    momenta set with `set_momenta` (`momenta`).  With `set_flow`, `step` can
-    also flow a copy of every field (the noise-off update, a gradient flow)
-    and measure the smoothed copies at up to four flow levels (`flow`).
+    momenta set with `set_momenta` (`momenta`).  With `set_flow`, `step`,
+    `step_flow` and `run_frames` can also flow a copy of every field (the
+    noise-off update, a gradient flow) and measure the smoothed copies at up
+    to four flow levels (`flow`).
 
     dtau, m2, lam and C are scalars or length-R sequences; seeds defaults to
     seed + r."""
@@ -714,7 +738,8 @@ class Phi4Ensemble:
         no momenta) is `step_flow(n, every, correlate)`: the measurements are
         taken of flowed copies of the fields, see there.  It is refused with
         ValueError, before any library call, with every < 1, momenta=True or
-        scheme="heun"."""
+        scheme="heun": Heun steps with the flow are `step_flow(...,
+        scheme="heun")`, which this keyword does not reach."""
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n, every = int(n), int(every)
@@ -734,24 +759,75 @@ class Phi4Ensemble:
         _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
         return ser
 
-    def step_flow(self, n=1, every=1, correlate=False):
-        """n Euler steps of every replica in one launch, as `step`, with a flow
+    def step_flow(self, n=1, every=1, correlate=False, scheme="euler"):
+        """n steps of every replica in one launch, as `step`, with a flow
         measurement after each every-th step (every >= 1, `set_flow` first;
-        sq_phi4_ens_step_flow): the kernel flows a copy of every field and
+        sq_phi4_ens_step_flow, with scheme="heun" sq_phi4_ens_step_flow_heun:
+        every step the Heun step): the kernel flows a copy of every field and
         measures at each of the F flow levels.  Returns the (n // every, F, R, 4)
         array of the flowed fields' sums; `correlate` adds one correlator
         measurement per level to the FLOW accumulators (`fcorr_sums`,
         `fcorrelator`), not to the plain ones.  Fields, counters and flags are
-        those of `step(n)`.  `step(n, every=k, flow=True, correlate=...)` is
-        this call."""
+        those of `step(n, scheme=scheme)`.  `step(n, every=k, flow=True,
+        correlate=...)` is this call with Euler steps; scheme="heun" is reached
+        here only (`step` refuses it with flow=True)."""
+        if scheme not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n, every = int(n), int(every)
         if every < 1:
             raise ValueError("a flow measurement needs every >= 1")
         ser = np.zeros((max(n, 0) // every, self._flow_levels(), self.R, 4))
-        _lib.call("sq_phi4_ens_step_flow", self._h, n, every, _dptr(ser) if ser.size else None,
-                  1 if correlate else 0)
+        _lib.call("sq_phi4_ens_step_flow_heun" if scheme == "heun" else "sq_phi4_ens_step_flow", self._h, n, every,
+                  _dptr(ser) if ser.size else None, 1 if correlate else 0)
         return ser
 
+    def run_frames_flow(self, n, correlate=False, scheme="euler"):
+        """n frames of every replica in one launch, as `run_frames(n,
+        scheme=scheme)`, with a flow measurement behind every frame's verdict
+        (`set_flow` first; sq_phi4_ens_run_frames_flow): (stable (n, R) bool,
+        dtau (n, R), series (n, F, R, 4)).  series[f] holds the F flow levels'
+        sums of the field each replica holds after frame f, the adopted field
+        after a stable frame, the frame's start field again after a rollback;
+        with level 0 among the levels that row is `run_frames(n,
+        measure=True)`'s series.  `correlate`: one correlator measurement per
+        level after every stable frame of a replica, added to the FLOW
+        accumulators (`fcorr_sums`, `fcorrelator`); a rolled-back frame adds
+        nothing.  Verdicts, dtau, fields, counters, flags and the stability
+        records are those of the call without the flow.  `run_frames(n,
+        flow=True, ...)` is this call."""
+        if scheme not in ("euler", "heun"):
+            raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
+        n = int(n)
+        st = np.zeros((max(n, 0), self.R), dtype=np.int32)
+        dt = np.zeros((max(n, 0), self.R))
+        ser = np.zeros((max(n, 0), self._flow_levels(), self.R, 4))
+        _lib.call("sq_phi4_ens_run_frames_flow", self._h, n, st.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dptr(dt),
+                  _dptr(ser) if ser.size else None, 1 if correlate else 0, 1 if scheme == "heun" else 0)
+        if n > 0:
+            self._frames_run = True
+        return st != 0, dt, ser
+
+    @staticmethod
+    def frames_flow_shape_info(shape):
+        """The LDS layout of the flow launches in frames and Heun steps for a
+        lattice of `shape` (sq_phi4_ens_frames_flow_shape_info; no device
+        needed): {"images" / "lds_bytes" of run_frames_flow without the
+        correlator (either scheme), "corr_images" / "corr_lds_bytes" with it,
+        "heun_step_images" / "heun_step_corr_images" / "heun_step_corr_lds_bytes"
+        of step_flow(scheme="heun"), "stash", "heun_stash", "heun_step_stash":
+        where the un-flowed field waits in Euler frames, Heun frames and Heun
+        steps (0 = registers, 1 = device memory), "mask": bit 2 * (scheme ==
+        "heun") + correlate set when run_frames_flow runs that combination on
+        the shape}."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 8)()
+        _lib.call("sq_phi4_ens_frames_flow_shape_info", dims, out)
+        o = [int(v) for v in out]
+        return {"images": o[0], "lds_bytes": o[1], "corr_images": o[2], "corr_lds_bytes": o[3],
+                "heun_step_images": o[4] & 0xff, "heun_step_corr_images": o[4] >> 8, "heun_step_corr_lds_bytes": o[5],
+                "stash": o[6] & 1, "heun_stash": (o[6] >> 1) & 1, "heun_step_stash": (o[6] >> 2) & 1, "mask": o[7]}
+
+    @_frames_accept_flow
     def run_frames(self, n, measure=False, correlate=False, momenta=False, scheme="euler"):
         """n frames of every replica in one launch: (stable (n, R) bool, dtau
         (n, R) after each frame), and with `measure` the (n, R, 4) sums S1, S2,
@@ -766,7 +842,13 @@ class Phi4Ensemble:
         stability record taken of φ' against the step's input; the rule, the
         rollback, the controller and the measurements are the same, and T, V,
         Δτ and the counters are shared with the Euler frames.  Calls of either
-        scheme, and raw steps, may alternate."""
+        scheme, and raw steps, may alternate.
+
+        The keyword-only flow=True (needs `set_flow`) is `run_frames_flow(n,
+        correlate, scheme)`: `measure` is ignored, the (n, F, R, 4) series of
+        the flowed fields' sums is always returned, and `correlate` feeds the
+        flow accumulators.  momenta=True is refused with ValueError before any
+        library call."""
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n = int(n)
