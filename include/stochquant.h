@@ -636,6 +636,66 @@ int sq_phi4_ens_step_heun(sq_phi4_ens *e, int nsteps, int every, double *series,
 int sq_phi4_ens_run_frames_heun(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, int measure);
 int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]);
 
+/* The Metropolis-adjusted Langevin (MALA) step of the phi^4 ensemble: the
+ * Euler update as a proposal, accepted or rejected per replica inside the
+ * resident kernel, so that the chain samples exp(-S / T), T = sig^2 / 2h ~
+ * C^2, with no step-size bias.  ABI 6: symbols added, none
+ * changed.
+ *
+ * One MALA step of replica r with record (h, m2, lam6, sig, sigq, key) at
+ * counter s holding phi.  Everything below is in double, formed from the
+ * float32 fields and the float record values converted to double.
+ *   1. Proposal: p = E(phi), the Euler update of sq_phi4_ens_step at counter s
+ *      with its normals and its guard: bit for bit what a step would store.
+ *   2. d(f)_x = sum_nb f - 6 f_x - f_x (m2 + lam6 f_x^2);
+ *      S(f) = (3 + m2 / 2) S2(f) - NN(f) + lam6 / 4 S4(f), S2, S4, NN the sums
+ *      of sq_phi4_ens_moments.
+ *   3. a_x = p_x - phi_x - h d(phi)_x,  b_x = phi_x - p_x - h d(p)_x.
+ *   4. dH = [2 h (S(p) - S(phi)) + 1/2 (sum b^2 - sum a^2)] / sig^2, sig the
+ *      record's float in double.  dH depends on (phi, p) and the record only,
+ *      not on the normals.  The order of summation is fixed (the head of
+ *      sq_phi4_ens_mala.hip states it): the same bits on every call, for any
+ *      nrep, and for calls split in any way.
+ *   5. u = (w + 0.5) 2^-32, w word 0 of Philox4x32-10 at the counter {0,
+ *      3 << 24, s lo, s hi} (stream 3, kStreamAccept) under the replica's key.
+ *   6. Verdict 2 (guard trip): the proposal's guard touched a site (max |p|
+ *      >= clamp): rejected, the replica's guard flag set.  Verdict 1 (accept):
+ *      dH <= 0 or u < exp(-dH), the device's double exp: the replica holds p.
+ *      Verdict 0 (reject) otherwise, a NaN dH included: the replica keeps phi
+ *      bit for bit.
+ *   7. The counter advances by one per MALA step, whatever the verdict.
+ *
+ * Limits.  A replica with sig == 0 (C = 0, or sqrt(2 dtau) C zero in fp32) has
+ * no proposal density: any such replica in the handle makes
+ * sq_phi4_ens_step_mala fail with SQ_E_STATE before anything is launched.
+ * MALA is for thermalised fields: from a cold (zero) field the first proposal
+ * is far rougher than equilibrium and nothing is accepted, so thermalise with
+ * Euler or Heun steps first.  At fixed dtau the acceptance falls with the
+ * volume; choose dtau by sq_phi4_ens_mala_stats.  Momenta, the gradient flow
+ * and frames do not run with MALA steps (the frames' stability rule and dtau
+ * controller have no meaning under an accept/reject step): measure with
+ * sq_phi4_ens_pslices / sq_phi4_ens_flowed between calls.
+ *
+ * sq_phi4_ens_step_mala: nsteps MALA steps of every replica in one launch.
+ * every, series: as sq_phi4_ens_step, counting MALA steps, the sums taken of
+ * the field the replica holds after the verdict.  measure: bit 0 adds what
+ * sq_phi4_ens_step_corr adds, of that field (one measurement per every-th
+ * step, also when the step was rejected), and needs every >= 1, else SQ_E_ARG;
+ * other bits: SQ_E_ARG.  rec, nullable: [nsteps][nrep][3] = dH, u, verdict of
+ * every step.  nsteps = 0 does nothing (after the argument and state checks).
+ * Calls of the three schemes alternate freely on one handle.
+ * sq_phi4_ens_perf counts one step per MALA step.
+ *
+ * sq_phi4_ens_mala_stats: out[r] = {proposed, accepted, guard trips} of
+ * replicas first .. first + count, accumulated over every MALA call since
+ * creation or the last sq_phi4_ens_mala_reset of the replica (which clears
+ * them; the guard FLAG is sq_phi4_ens_flags').  Range errors: SQ_E_ARG. */
+#define SQ_SCHEME_MALA 2
+int sq_phi4_ens_step_mala(sq_phi4_ens *e, int nsteps, int every, double *series /*[nsteps/every][R][4]*/,
+                          int measure /*bit 0: correlate*/, double *rec /*[nsteps][R][3], nullable*/);
+int sq_phi4_ens_mala_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][3]*/);
+int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

@@ -18,8 +18,8 @@ KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize", "VGPRs Spill", "Occupancy
 
 def resources(src, extra=()):
     sys.path.insert(0, ROOT)
-    from stochquant_amd.build import COMMON, HIPCC, ARCH
-    cmd = [HIPCC] + COMMON + [f"--offload-arch={ARCH}", "-x", "hip", "-c", src, "-o", os.devnull,
+    from stochquant_amd.build import COMMON, EXTRA_FLAGS, HIPCC, ARCH
+    cmd = [HIPCC] + COMMON + EXTRA_FLAGS.get(os.path.basename(src), []) + [f"--offload-arch={ARCH}", "-x", "hip", "-c", src, "-o", os.devnull,
                               "-Rpass-analysis=kernel-resource-usage"] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

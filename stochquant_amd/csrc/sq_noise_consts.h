@@ -43,6 +43,7 @@ static_assert(kPhiloxM1 * kPhiloxM1Inv == 1u, "M1 inverse");
 constexpr uint32_t kStreamField = 0;  // per-site field noise
 constexpr uint32_t kStreamOmega = 1;  // QM1D collective coordinate
 constexpr uint32_t kStreamInit = 2;   // initial field
+constexpr uint32_t kStreamAccept = 3; // the MALA step's accept/reject uniform (quad 0, one draw per replica and step)
 
 struct Phi4NoiseConsts {
     uint32_t u0, u1, a0, b0, b2, u3, d2;

@@ -62,6 +62,10 @@ struct sq_phi4_ens {
     size_t fG_cap = 0;                   // ... in levels
     double *ftmp = nullptr;              // sq_phi4_ens_flowed's / _flow_field's device buffer
     size_t ftmp_cap = 0;                 // ... in bytes
+    long long *mstat = nullptr;          // [R][3] MALA counters: proposed, accepted, guard trips (first MALA call on);
+                                         // cleared by sq_phi4_ens_mala_reset only
+    double *mrec = nullptr;              // the last MALA call's per-step records: pinned host memory the kernel writes
+    size_t mrec_cap = 0;                 // ... in doubles
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -161,6 +165,11 @@ void release_phi4_ens(sq_phi4_ens *e) {
     (void)hipFree(e->fS1);
     (void)hipFree(e->fN);
     (void)hipFree(e->ftmp);
+    (void)hipFree(e->mstat);
+    (void)hipHostFree(e->mrec);
+    e->mstat = nullptr;
+    e->mrec = nullptr;
+    e->mrec_cap = 0;
     e->frec = nullptr;
     e->fG = e->fS1 = e->ftmp = nullptr;
     e->fN = nullptr;
@@ -1208,6 +1217,101 @@ int sq_phi4_ens_perf(sq_phi4_ens *e, sq_perf_t *out) {
     out->steps = e->steps_total;
     out->site_updates = e->steps_total * (long long)e->sites;
     out->kernel_launches = e->launches;
+    return SQ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The MALA counters, allocated and zeroed at the first use.
+int ens_mala_stat(sq_phi4_ens *e) {
+    if (e->mstat) return SQ_OK;
+    const size_t bytes = sizeof(long long) * 3 * (size_t)e->R;
+    SQ_HIP(hipMalloc(&e->mstat, bytes));
+    SQ_HIP(hipMemset(e->mstat, 0, bytes));
+    SQ_HIP(hipDeviceSynchronize());  // the memset ran on the null stream
+    return SQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_step_mala(sq_phi4_ens *e, int nsteps, int every, double *series, int measure, double *rec) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a MALA step measures no momenta");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
+    for (int r = 0; r < e->R; ++r)
+        if (ens_rec(e->rep[(size_t)r]).sig == 0.0f)
+            return fail(SQ_E_STATE, "a MALA step needs C != 0 in every replica (sig = sqrt(2 dtau) C is zero in fp32): "
+                                    "without noise there is no proposal density");
+    if (nsteps == 0) return SQ_OK;
+    const bool corr = (measure & 1) != 0;
+    DeviceGuard g(e->dev);
+    int rc = ens_sync_recs(e);
+    if (rc) return rc;
+    rc = ens_mala_stat(e);
+    if (rc) return rc;
+    const size_t nrec = (every > 0 && series) ? (size_t)(nsteps / every) : 0;
+    const size_t nd = nrec * (size_t)e->R * 4;
+    if (nd > e->series_cap) {  // as ens_step
+        (void)hipHostFree(e->series);
+        e->series = nullptr;
+        e->series_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
+        e->series_cap = nd;
+    }
+    const size_t nm = rec ? (size_t)nsteps * (size_t)e->R * 3 : 0;
+    if (nm > e->mrec_cap) {
+        (void)hipHostFree(e->mrec);
+        e->mrec = nullptr;
+        e->mrec_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->mrec, sizeof(double) * nm, hipHostMallocDefault));
+        e->mrec_cap = nm;
+    }
+    sq::Phi4EnsArgs a = ens_args(e);
+    a.nsteps = nsteps;
+    a.every = (nd || corr) ? every : 0;
+    a.series = nd ? e->series : nullptr;
+    sq::Phi4EnsMalaArgs w{};
+    w.stat = e->mstat;
+    w.rec = nm ? e->mrec : nullptr;
+    const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+    SQ_HIP(sq::phi4_ens_mala_launch(a, w, corr ? &c : nullptr, e->R, e->stream));
+    e->launches++;
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    if (nm) memcpy(rec, e->mrec, sizeof(double) * nm);
+    e->adv += (unsigned long long)nsteps;
+    for (auto &r : e->rep) r.step += (unsigned long long)nsteps;
+    e->steps_total += (long long)nsteps * e->R;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_mala_stats(sq_phi4_ens *e, int first, int count, long long *out) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!out) return fail(SQ_E_ARG, "null argument");
+    if (count == 0) return SQ_OK;
+    if (!e->mstat) {  // no MALA step yet
+        memset(out, 0, sizeof(long long) * 3 * (size_t)count);
+        return SQ_OK;
+    }
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemcpy(out, e->mstat + 3 * (size_t)first, sizeof(long long) * 3 * (size_t)count, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0 || !e->mstat) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemset(e->mstat + 3 * (size_t)first, 0, sizeof(long long) * 3 * (size_t)count));
+    SQ_HIP(hipDeviceSynchronize());
     return SQ_OK;
 }
 

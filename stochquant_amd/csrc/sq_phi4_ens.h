@@ -156,6 +156,21 @@ hipError_t phi4_ens_heun_launch(const Phi4EnsArgs &a, const Phi4EnsCorrArgs *c, 
 // rules are those of the three frames launches; the image count selects the instance.
 hipError_t phi4_ens_heun_frames_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsCorrArgs *c,
                                        const Phi4EnsPCorrArgs *p, int nrep, hipStream_t s);
+// ---- the Metropolis-adjusted Langevin step (sq_phi4_ens_mala.hip) ----
+// The replicas' counters, accumulated in place, and the launch's optional per-step record.
+struct Phi4EnsMalaArgs {
+    long long *stat;  // [R][3] = proposed, accepted, guard trips (device memory)
+    double *rec;      // [nsteps][R][3] = dH, u, verdict (0 rejected, 1 accepted, 2 guard trip), device-visible
+                      // (pinned host memory); nullable
+};
+// nsteps MALA steps of every replica in one launch (phi4_ens_mala_kernel): per step the Euler update of the step
+// launch as the proposal, accepted or rejected per replica inside the kernel; the counter advances by one per
+// step whatever the verdict.  Every replica's sig must be non-zero (the caller checks: the kernel divides by
+// sig^2).  c nullable: the measurement of phi4_ens_step_corr_launch after each every-th step, of the field the
+// replica then holds.  The work-group shape, the LDS layout and the argument rules are those of the step launches.
+hipError_t phi4_ens_mala_launch(const Phi4EnsArgs &a, const Phi4EnsMalaArgs &w, const Phi4EnsCorrArgs *c, int nrep,
+                                hipStream_t s);
+
 // ---- gradient-flow measurements (sq_phi4_ens_flow.hip) ----
 constexpr int kPhi4EnsMaxFlowLevels = 4;    // SQ_PHI4_ENS_MAX_FLOW_LEVELS
 constexpr int kPhi4EnsMaxFlowSteps = 4096;  // SQ_PHI4_ENS_MAX_FLOW_STEPS

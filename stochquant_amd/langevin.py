@@ -514,6 +514,10 @@ class Phi4Lattice(_Ctx):
         _lib.call("sq_p2p_connect", self._h, buf, len(blobs))
 
 
+_MALA_NO_FRAMES = ("frames do not run with scheme='mala': the stability rule and the dtau controller have no meaning "
+                   "under an accept/reject step (use step(scheme='mala') and mala_stats())")
+
+
 def _accepts_flow(step):
     """`Phi4Ensemble.step` with the keyword-only `flow`: flow=True hands the call
     to `step_flow` after refusing what the flow does not run with.  The
@@ -528,8 +532,10 @@ def _accepts_flow(step):
         a = sig.bind(self, *args, **kw)
         a.apply_defaults()
         a = a.arguments
+        if a["scheme"] == "mala":
+            raise ValueError("scheme='mala' does not run with flow=True (use flowed() between calls)")
         if a["scheme"] not in ("euler", "heun"):
-            raise ValueError(f"scheme must be 'euler' or 'heun', not {a['scheme']!r}")
+            raise ValueError(f"scheme must be 'euler', 'heun' or 'mala', not {a['scheme']!r}")
         if a["momenta"]:
             raise ValueError("flow=True does not run with momenta=True (use flowed() between calls)")
         if a["scheme"] == "heun":
@@ -553,6 +559,8 @@ def _frames_accept_flow(run_frames):
         a = sig.bind(self, *args, **kw)
         a.apply_defaults()
         a = a.arguments
+        if a["scheme"] == "mala":
+            raise ValueError(_MALA_NO_FRAMES)
         if a["scheme"] not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {a['scheme']!r}")
         if a["momenta"]:
@@ -734,14 +742,24 @@ class Phi4Ensemble:
         step, and `every`, `correlate` and `momenta` count and measure Heun
         steps.  Calls of either scheme may alternate.
 
+        scheme="mala": the Metropolis-adjusted Langevin step, `step_mala(n,
+        every, correlate)` (see there): the Euler update as a proposal, accepted
+        or rejected per replica in the kernel, no step-size bias.  momenta=True
+        and flow=True are refused with ValueError before any library call (use
+        `pslices()` / `flowed()` between calls).
+
         The keyword-only flow=True (needs every >= 1 and `set_flow`; Euler steps,
         no momenta) is `step_flow(n, every, correlate)`: the measurements are
         taken of flowed copies of the fields, see there.  It is refused with
         ValueError, before any library call, with every < 1, momenta=True or
         scheme="heun": Heun steps with the flow are `step_flow(...,
         scheme="heun")`, which this keyword does not reach."""
+        if scheme == "mala":
+            if momenta:
+                raise ValueError("scheme='mala' does not run with momenta=True (use pslices() between calls)")
+            return self.step_mala(n, every, correlate=correlate)
         if scheme not in ("euler", "heun"):
-            raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
+            raise ValueError(f"scheme must be 'euler', 'heun' or 'mala', not {scheme!r}")
         n, every = int(n), int(every)
         fn, extra = "sq_phi4_ens_step", ()
         if correlate or momenta:
@@ -759,6 +777,50 @@ class Phi4Ensemble:
         _lib.call(fn, self._h, n, every, _dptr(ser) if ser.size else None, *extra)
         return ser
 
+    def step_mala(self, n=1, every=0, correlate=False, record=False):
+        """n Metropolis-adjusted Langevin (MALA) steps of every replica in one
+        launch (sq_phi4_ens_step_mala; include/stochquant.h has the definition).
+        Per step and replica the Euler update of `step` is a proposal p; the
+        kernel forms dH = [2h (S(p) - S(φ)) + ½ (Σb² - Σa²)] / σ² in double from
+        the two fields, draws one uniform u from the replica's Philox key, and
+        the replica holds p when dH <= 0 or u < exp(-dH), else it keeps φ bit
+        for bit.  The chain samples exp(-S / C²) with no Δτ bias; the counter
+        advances by one per step whatever the verdict.  A proposal that reached
+        the clamp is rejected and sets the replica's guard flag.
+
+        every = k > 0: returns the (n // k, R, 4) sums of the field each
+        replica holds after every k-th step's verdict, else None; `correlate`
+        (needs every >= 1) adds one correlator measurement of that field per
+        record, also after a rejected step.  record=True: returns (series,
+        rec), rec the (n, R, 3) array of (dH, u, verdict) of every step, verdict
+        0 rejected, 1 accepted, 2 guard trip.
+
+        Use: thermalise with Euler or Heun steps first (from a cold field
+        nothing is accepted), then choose Δτ by `mala_stats()`: the acceptance
+        falls with the volume at fixed Δτ.  Every replica needs C != 0
+        (StochQuantError otherwise).  Calls of the three schemes may alternate."""
+        n, every = int(n), int(every)
+        if correlate and every < 1:
+            raise ValueError("correlate=True needs every >= 1")
+        ser = np.zeros((max(n, 0) // every, self.R, 4)) if every > 0 else None
+        rec = np.zeros((max(n, 0), self.R, 3)) if record else None
+        _lib.call("sq_phi4_ens_step_mala", self._h, n, every,
+                  _dptr(ser) if ser is not None and ser.size else None, 1 if correlate else 0,
+                  _dptr(rec) if rec is not None and rec.size else None)
+        return (ser, rec) if record else ser
+
+    def mala_stats(self, first=0, count=None):
+        """(count, 3) int64: MALA steps proposed, accepted and rejected by the
+        guard, per replica, since creation or `mala_reset` (sq_phi4_ens_mala_stats)."""
+        k = self._count(first, count)
+        out = np.zeros((max(k, 0), 3), dtype=np.int64)
+        _lib.call("sq_phi4_ens_mala_stats", self._h, int(first), k, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def mala_reset(self, first=0, count=None):
+        """Clear the MALA counters of replicas first .. first + count."""
+        _lib.call("sq_phi4_ens_mala_reset", self._h, int(first), self._count(first, count))
+
     def step_flow(self, n=1, every=1, correlate=False, scheme="euler"):
         """n steps of every replica in one launch, as `step`, with a flow
         measurement after each every-th step (every >= 1, `set_flow` first;
@@ -771,6 +833,8 @@ class Phi4Ensemble:
         those of `step(n, scheme=scheme)`.  `step(n, every=k, flow=True,
         correlate=...)` is this call with Euler steps; scheme="heun" is reached
         here only (`step` refuses it with flow=True)."""
+        if scheme == "mala":
+            raise ValueError("scheme='mala' does not run with the flow (use flowed() between calls)")
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n, every = int(n), int(every)
@@ -795,6 +859,8 @@ class Phi4Ensemble:
         nothing.  Verdicts, dtau, fields, counters, flags and the stability
         records are those of the call without the flow.  `run_frames(n,
         flow=True, ...)` is this call."""
+        if scheme == "mala":
+            raise ValueError(_MALA_NO_FRAMES)
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n = int(n)
@@ -848,7 +914,10 @@ class Phi4Ensemble:
         correlate, scheme)`: `measure` is ignored, the (n, F, R, 4) series of
         the flowed fields' sums is always returned, and `correlate` feeds the
         flow accumulators.  momenta=True is refused with ValueError before any
-        library call."""
+        library call.  scheme="mala" is refused likewise: frames have no
+        meaning under an accept/reject step."""
+        if scheme == "mala":
+            raise ValueError(_MALA_NO_FRAMES)
         if scheme not in ("euler", "heun"):
             raise ValueError(f"scheme must be 'euler' or 'heun', not {scheme!r}")
         n = int(n)
