@@ -696,6 +696,75 @@ int sq_phi4_ens_step_mala(sq_phi4_ens *e, int nsteps, int every, double *series 
 int sq_phi4_ens_mala_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][3]*/);
 int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count);
 
+/* Hybrid Monte Carlo (HMC) trajectories of the phi^4 ensemble: the momentum
+ * drawn once, L leapfrog steps, one Metropolis test, inside the resident
+ * kernel.  The MALA proposal is one leapfrog step of step
+ * length sig = C sqrt(2 dtau) with force -dS / C^2; a trajectory is L of them,
+ * so the chain samples exp(-S / C^2) with no step-size bias and moves
+ * ballistically, not diffusively, over L sig.  ABI 6: symbols added, none
+ * changed.
+ *
+ * One trajectory of replica r with record (h = dtau, m2, lam6, sig, sigq, key)
+ * at counter s holding phi_0.  d(f) is the Euler update's drift, fp32, in the
+ * update's operation order; guard is the update's guard (NaN -> +clamp, else
+ * clipped to [-clamp, clamp]).
+ *   1. Length: L = nleap, or, with randomize != 0,
+ *      L = 1 + ((uint64) o.y * nleap >> 32), o the Philox4x32-10 block of the
+ *      accept uniform: counter {0, 3 << 24, s lo, s hi} under the replica's
+ *      key; o.x stays the uniform, u = (o.x + 0.5) 2^-32.  1 <= nleap <=
+ *      SQ_PHI4_ENS_MAX_LEAP.
+ *   2. First step: phi_1 = E_s(phi_0), the Euler update of sq_phi4_ens_step at
+ *      counter s: MALA's proposal bit for bit (sig xi = sig pi_0).
+ *   3. Interior steps, k = 1 .. L - 1 (Stoermer-Verlet in displacement form):
+ *      g = guard(fma(2h, d(phi_k), phi_k)), t = phi_k - phi_{k-1} (fp32),
+ *      phi_{k+1} = guard(g + t).  2h is the float h doubled: g is the noise-off
+ *      update at step size 2h bit for bit.  No noise is drawn, no counter moves.
+ *   4. dH = [2 h (S(phi_L) - S(phi_0)) + 1/2 (sum b^2 - sum a^2)] / sig^2,
+ *      a = phi_1 - phi_0 - h d(phi_0), b = phi_{L-1} - phi_L - h d(phi_L), in
+ *      double with MALA's per-site term, d and S as in the MALA definition above:
+ *      the lane's accumulator takes -t(phi_0, phi_1) behind step 1 and
+ *      +t(phi_L, phi_{L-1}) behind the last step; the wave sum and the fold in
+ *      wave order are MALA's.  For L = 1 this is MALA's dH operation for
+ *      operation.  (sig pi_L = -b: dH = H(phi_L, pi_L) - H(phi_0, pi_0), H =
+ *      pi^2 / 2 + S / C^2.)
+ *   5. Verdict 2 (guard trip) if phi_1, any g or any phi_k reaches clamp in
+ *      magnitude; else 1 (accept) if dH <= 0 or u < exp(-dH); else 0.  On 1 the
+ *      replica holds phi_L; on 0 or 2 it keeps phi_0 bit for bit; on 2 its guard
+ *      flag is set.
+ *   6. The counter advances by one per trajectory, whatever L and the verdict.
+ * nleap = 1 is sq_phi4_ens_step_mala bit for bit, with or without randomize.
+ *
+ * Fixed or random lengths.  A fixed L is non-ergodic where omega L sig comes
+ * near a multiple of pi for some mode of frequency omega: that mode returns to
+ * where it started (free 8x4x4 lattice, dtau 0.02: nleap = 16 fixed gives
+ * <phi^2> = 0.185 against the exact 0.1727).  Fixed lengths are for short
+ * trajectories and for tests; use randomize for production: the lengths are
+ * then uniform on 1 .. nleap, drawn independently of the momenta, which keeps
+ * detailed balance and removes the resonances.
+ *
+ * Limits: MALA's.  A replica with sig == 0 makes sq_phi4_ens_step_hmc fail with
+ * SQ_E_STATE before anything is launched; thermalise with Euler or Heun steps
+ * first; momenta, the gradient flow and frames do not run with trajectories.
+ *
+ * sq_phi4_ens_step_hmc: ntraj trajectories of every replica in one launch.
+ * every, series, measure: as sq_phi4_ens_step_mala, counting trajectories, of
+ * the field held after the verdict.  rec, nullable: [ntraj][nrep][4] = dH, u,
+ * verdict, L.  Errors are MALA's, and nleap outside [1, SQ_PHI4_ENS_MAX_LEAP]:
+ * SQ_E_ARG; all before any device work.  ntraj = 0 does nothing (after the
+ * checks).  Calls of the four schemes alternate freely on one handle.
+ * sq_phi4_ens_perf counts one step per trajectory.
+ *
+ * sq_phi4_ens_hmc_stats: out[r] = {trajectories, accepted, guard trips,
+ * leapfrog steps} of replicas first .. first + count since creation or the last
+ * sq_phi4_ens_hmc_reset of the replica.  The MALA counters are separate. */
+#define SQ_SCHEME_HMC 3
+#define SQ_PHI4_ENS_MAX_LEAP 4096
+int sq_phi4_ens_step_hmc(sq_phi4_ens *e, int ntraj, int nleap, int randomize, int every,
+                         double *series /*[ntraj/every][R][4]*/, int measure /*bit 0: correlate*/,
+                         double *rec /*[ntraj][R][4], nullable*/);
+int sq_phi4_ens_hmc_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][4]*/);
+int sq_phi4_ens_hmc_reset(sq_phi4_ens *e, int first, int count);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

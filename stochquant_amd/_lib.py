@@ -226,6 +226,9 @@ SIGNATURES = {
     "sq_phi4_ens_step_mala": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
     "sq_phi4_ens_mala_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ens_mala_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_step_hmc": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
+    "sq_phi4_ens_hmc_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ens_hmc_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4

@@ -66,6 +66,10 @@ struct sq_phi4_ens {
                                          // cleared by sq_phi4_ens_mala_reset only
     double *mrec = nullptr;              // the last MALA call's per-step records: pinned host memory the kernel writes
     size_t mrec_cap = 0;                 // ... in doubles
+    long long *hstat = nullptr;          // [R][4] HMC counters: trajectories, accepted, guard trips, leapfrog steps
+                                         // (first HMC call on); cleared by sq_phi4_ens_hmc_reset only
+    double *hrec = nullptr;              // the last HMC call's per-trajectory records: pinned host memory
+    size_t hrec_cap = 0;                 // ... in doubles
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -170,6 +174,11 @@ void release_phi4_ens(sq_phi4_ens *e) {
     e->mstat = nullptr;
     e->mrec = nullptr;
     e->mrec_cap = 0;
+    (void)hipFree(e->hstat);
+    (void)hipHostFree(e->hrec);
+    e->hstat = nullptr;
+    e->hrec = nullptr;
+    e->hrec_cap = 0;
     e->frec = nullptr;
     e->fG = e->fS1 = e->ftmp = nullptr;
     e->fN = nullptr;
@@ -1311,6 +1320,105 @@ int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count) {
     if (count == 0 || !e->mstat) return SQ_OK;
     DeviceGuard g(e->dev);
     SQ_HIP(hipMemset(e->mstat + 3 * (size_t)first, 0, sizeof(long long) * 3 * (size_t)count));
+    SQ_HIP(hipDeviceSynchronize());
+    return SQ_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The HMC counters, allocated and zeroed at the first use.
+int ens_hmc_stat(sq_phi4_ens *e) {
+    if (e->hstat) return SQ_OK;
+    const size_t bytes = sizeof(long long) * 4 * (size_t)e->R;
+    SQ_HIP(hipMalloc(&e->hstat, bytes));
+    SQ_HIP(hipMemset(e->hstat, 0, bytes));
+    SQ_HIP(hipDeviceSynchronize());  // the memset ran on the null stream
+    return SQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_step_hmc(sq_phi4_ens *e, int ntraj, int nleap, int randomize, int every, double *series, int measure,
+                         double *rec) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (ntraj < 0) return fail(SQ_E_ARG, "ntraj must be >= 0");
+    if (nleap < 1 || nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap must lie in [1, 4096]");
+    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a trajectory measures no momenta");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
+    for (int r = 0; r < e->R; ++r)
+        if (ens_rec(e->rep[(size_t)r]).sig == 0.0f)
+            return fail(SQ_E_STATE, "a trajectory needs C != 0 in every replica (sig = sqrt(2 dtau) C is zero in fp32): "
+                                    "without noise there is no momentum to draw");
+    if (ntraj == 0) return SQ_OK;
+    const bool corr = (measure & 1) != 0;
+    DeviceGuard g(e->dev);
+    int rc = ens_sync_recs(e);
+    if (rc) return rc;
+    rc = ens_hmc_stat(e);
+    if (rc) return rc;
+    const size_t nrec = (every > 0 && series) ? (size_t)(ntraj / every) : 0;
+    const size_t nd = nrec * (size_t)e->R * 4;
+    if (nd > e->series_cap) {  // as ens_step
+        (void)hipHostFree(e->series);
+        e->series = nullptr;
+        e->series_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->series, sizeof(double) * nd, hipHostMallocDefault));
+        e->series_cap = nd;
+    }
+    const size_t nm = rec ? (size_t)ntraj * (size_t)e->R * 4 : 0;
+    if (nm > e->hrec_cap) {
+        (void)hipHostFree(e->hrec);
+        e->hrec = nullptr;
+        e->hrec_cap = 0;
+        SQ_HIP(hipHostMalloc(&e->hrec, sizeof(double) * nm, hipHostMallocDefault));
+        e->hrec_cap = nm;
+    }
+    sq::Phi4EnsArgs a = ens_args(e);
+    a.nsteps = ntraj;
+    a.every = (nd || corr) ? every : 0;
+    a.series = nd ? e->series : nullptr;
+    sq::Phi4EnsHmcArgs w{};
+    w.stat = e->hstat;
+    w.rec = nm ? e->hrec : nullptr;
+    w.nleap = nleap;
+    w.randomize = randomize != 0 ? 1 : 0;
+    const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+    SQ_HIP(sq::phi4_ens_hmc_launch(a, w, corr ? &c : nullptr, e->R, e->stream));
+    e->launches++;
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    if (nm) memcpy(rec, e->hrec, sizeof(double) * nm);
+    e->adv += (unsigned long long)ntraj;  // one count per trajectory
+    for (auto &r : e->rep) r.step += (unsigned long long)ntraj;
+    e->steps_total += (long long)ntraj * e->R;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_hmc_stats(sq_phi4_ens *e, int first, int count, long long *out) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!out) return fail(SQ_E_ARG, "null argument");
+    if (count == 0) return SQ_OK;
+    if (!e->hstat) {  // no trajectory yet
+        memset(out, 0, sizeof(long long) * 4 * (size_t)count);
+        return SQ_OK;
+    }
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemcpy(out, e->hstat + 4 * (size_t)first, sizeof(long long) * 4 * (size_t)count, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_hmc_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0 || !e->hstat) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemset(e->hstat + 4 * (size_t)first, 0, sizeof(long long) * 4 * (size_t)count));
     SQ_HIP(hipDeviceSynchronize());
     return SQ_OK;
 }

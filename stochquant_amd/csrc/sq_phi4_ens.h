@@ -171,8 +171,27 @@ struct Phi4EnsMalaArgs {
 hipError_t phi4_ens_mala_launch(const Phi4EnsArgs &a, const Phi4EnsMalaArgs &w, const Phi4EnsCorrArgs *c, int nrep,
                                 hipStream_t s);
 
+// ---- hybrid Monte Carlo trajectories (sq_phi4_ens_hmc.hip) ----
+constexpr int kPhi4EnsMaxLeap = 4096;  // leapfrog steps per trajectory
+// The replicas' counters, accumulated in place, the trajectory length and the launch's optional record.
+struct Phi4EnsHmcArgs {
+    long long *stat;  // [R][4] = trajectories, accepted, guard trips, leapfrog steps (device memory)
+    double *rec;      // [nsteps][R][4] = dH, u, verdict (0 rejected, 1 accepted, 2 guard trip), L, device-visible
+                      // (pinned host memory); nullable
+    int nleap;        // 1 .. kPhi4EnsMaxLeap
+    int randomize;    // != 0: L = 1 + (o.y nleap >> 32) per trajectory, else L = nleap
+};
+// nsteps trajectories of every replica in one launch (phi4_ens_hmc_kernel): the Euler update of the step launch as
+// the first leapfrog step, L - 1 noise-free steps in displacement form, one Metropolis test; the counter advances
+// by one per trajectory whatever L and the verdict.  L = 1 is phi4_ens_mala_launch's step bit for bit.  The
+// replica's row of a.field holds the trajectory's start field during the call.  Every replica's sig must be
+// non-zero (the caller checks).  c, the work-group shape, the LDS layout and the argument rules: as
+// phi4_ens_mala_launch.
+hipError_t phi4_ens_hmc_launch(const Phi4EnsArgs &a, const Phi4EnsHmcArgs &w, const Phi4EnsCorrArgs *c, int nrep,
+                               hipStream_t s);
+
 // ---- gradient-flow measurements (sq_phi4_ens_flow.hip) ----
-constexpr int kPhi4EnsMaxFlowLevels = 4;    // SQ_PHI4_ENS_MAX_FLOW_LEVELS
+constexpr int kPhi4EnsMaxFlowLevels = 4;   // SQ_PHI4_ENS_MAX_FLOW_LEVELS
 constexpr int kPhi4EnsMaxFlowSteps = 4096;  // SQ_PHI4_ENS_MAX_FLOW_STEPS
 
 // One replica's flow coefficients: phi4_base_args' expressions of the flow step, its m² and λ; sig = 0.

@@ -62,50 +62,11 @@
 // scratch (ens_fold), since a slow wave may still be folding the step's totals.
 #define SQ_PHI4_ENS_KERNELS_ONLY
 #include "sq_phi4_ens.hip"
+#include "sq_phi4_ens_mala_dev.h"  // MalaCoef, mala_site, mala_quad
 
 namespace sq {
 
 namespace {
-
-struct MalaCoef {  // block-uniform, the float record in double
-    double h, h4, km, l4, m2, lam6;
-};
-
-// acc +- 2 t(f, o), the site's term of 2 sig^2 dH (see the head of the file); o: the other field at the site.
-// Fused multiply-adds where the head of the file writes them: 17 double operations per site (the vector fp64
-// rate is what a MALA step costs beyond a Heun step).
-template <bool SUB>
-__device__ __forceinline__ void mala_site(const MalaCoef &M, double &acc, double f, double o, double xm, double xp,
-                                          double ym, double yp, double zm, double zp) {
-#pragma clang fp contract(off)
-    const double f2 = f * f;
-    const double fw = (xp + yp) + zp;
-    const double nb = ((xm + ym) + zm) + fw;
-    const double lap = __builtin_fma(-6.0, f, nb);
-    const double g = __builtin_fma(M.lam6, f2, M.m2);
-    const double d = __builtin_fma(-f, g, lap);
-    const double e = __builtin_fma(M.l4, f2 * f2, __builtin_fma(M.km, f2, -(f * fw)));
-    const double t = __builtin_fma(-M.h, d, o - f);
-    acc = __builtin_fma(SUB ? -t : t, t, acc);
-    acc = __builtin_fma(SUB ? -M.h4 : M.h4, e, acc);
-}
-
-template <bool SUB>
-__device__ __forceinline__ void mala_quad(const MalaCoef &M, double &acc, const float4 &f, const float4 &o, float lft,
-                                          float rgt, const float4 &up, const float4 &dn, const float4 &zm,
-                                          const float4 &zp) {
-    // one site after the other (the scheduler would otherwise convert the quad's 26 floats at once and keep
-    // four sites' doubles in flight: the K = 8 instances have no registers for that)
-    __builtin_amdgcn_sched_barrier(0);
-    mala_site<SUB>(M, acc, f.x, o.x, lft, f.y, up.x, dn.x, zm.x, zp.x);
-    __builtin_amdgcn_sched_barrier(0);
-    mala_site<SUB>(M, acc, f.y, o.y, f.x, f.z, up.y, dn.y, zm.y, zp.y);
-    __builtin_amdgcn_sched_barrier(0);
-    mala_site<SUB>(M, acc, f.z, o.z, f.y, f.w, up.z, dn.z, zm.z, zp.z);
-    __builtin_amdgcn_sched_barrier(0);
-    mala_site<SUB>(M, acc, f.w, o.w, f.z, rgt, up.w, dn.w, zm.w, zp.w);
-    __builtin_amdgcn_sched_barrier(0);
-}
 
 // Stages 1 and 2 of one MALA step of the lane's K quads.  On return the waves' totals of 2 sig^2 dH and of
 // max |p| after the guard lie in the scratch (doubles scr[w], floats behind them), not yet behind a barrier;

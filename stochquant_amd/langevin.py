@@ -518,6 +518,13 @@ _MALA_NO_FRAMES = ("frames do not run with scheme='mala': the stability rule and
                    "under an accept/reject step (use step(scheme='mala') and mala_stats())")
 
 
+def _refuse_hmc(scheme, what):
+    """Trajectories have an interface of their own: no call that takes a scheme runs them."""
+    if scheme == "hmc":
+        raise ValueError(f"{what} does not run with scheme='hmc': trajectories are step_hmc(n, nleap, ...), which takes "
+                         "their length (momenta, the flow and frames do not run with them, as with scheme='mala')")
+
+
 def _accepts_flow(step):
     """`Phi4Ensemble.step` with the keyword-only `flow`: flow=True hands the call
     to `step_flow` after refusing what the flow does not run with.  The
@@ -532,6 +539,7 @@ def _accepts_flow(step):
         a = sig.bind(self, *args, **kw)
         a.apply_defaults()
         a = a.arguments
+        _refuse_hmc(a["scheme"], "step")
         if a["scheme"] == "mala":
             raise ValueError("scheme='mala' does not run with flow=True (use flowed() between calls)")
         if a["scheme"] not in ("euler", "heun"):
@@ -559,6 +567,7 @@ def _frames_accept_flow(run_frames):
         a = sig.bind(self, *args, **kw)
         a.apply_defaults()
         a = a.arguments
+        _refuse_hmc(a["scheme"], "run_frames")
         if a["scheme"] == "mala":
             raise ValueError(_MALA_NO_FRAMES)
         if a["scheme"] not in ("euler", "heun"):
@@ -754,6 +763,7 @@ class Phi4Ensemble:
         ValueError, before any library call, with every < 1, momenta=True or
         scheme="heun": Heun steps with the flow are `step_flow(...,
         scheme="heun")`, which this keyword does not reach."""
+        _refuse_hmc(scheme, "step")
         if scheme == "mala":
             if momenta:
                 raise ValueError("scheme='mala' does not run with momenta=True (use pslices() between calls)")
@@ -821,6 +831,61 @@ class Phi4Ensemble:
         """Clear the MALA counters of replicas first .. first + count."""
         _lib.call("sq_phi4_ens_mala_reset", self._h, int(first), self._count(first, count))
 
+    def step_hmc(self, n=1, nleap=1, randomize=False, every=0, correlate=False, record=False):
+        """n hybrid Monte Carlo (HMC) trajectories of every replica in one launch
+        (sq_phi4_ens_step_hmc; include/stochquant.h has the definition).  Per
+        trajectory and replica the momentum is drawn once -- the first leapfrog
+        step is the Euler update of `step`, MALA's proposal --, L - 1 noise-free
+        leapfrog steps of step length σ = C sqrt(2Δτ) follow in the kernel, and
+        one Metropolis test on dH, formed in double from the two end fields,
+        decides: the replica holds φ_L or keeps its field bit for bit.  The
+        chain samples exp(-S / C²) with no Δτ bias and moves a distance L σ per
+        test where MALA moves σ.  The counter advances by one per trajectory.
+        nleap=1 is `step_mala` bit for bit.
+
+        L = nleap, or with randomize=True uniform on 1 .. nleap per trajectory
+        and replica, from the Philox block of the accept uniform.  A fixed
+        length is non-ergodic where ω L σ nears a multiple of π for some mode
+        (that mode returns to where it started): fixed lengths are for short
+        trajectories and tests, randomize=True is for production.
+        1 <= nleap <= 4096.
+
+        every = k > 0: returns the (n // k, R, 4) sums of the field each
+        replica holds after every k-th trajectory's verdict, else None;
+        `correlate` (needs every >= 1) adds one correlator measurement of that
+        field per record.  record=True: returns (series, rec), rec the (n, R, 4)
+        array of (dH, u, verdict, L) of every trajectory, verdict 0 rejected, 1
+        accepted, 2 guard trip (some field of the trajectory reached the clamp:
+        rejected, the replica's guard flag set).
+
+        Use as `step_mala`: thermalise first, choose Δτ and nleap by
+        `hmc_stats()`; every replica needs C != 0 (StochQuantError otherwise).
+        Calls of the four schemes may alternate."""
+        n, nleap, every = int(n), int(nleap), int(every)
+        if nleap < 1 or nleap > 4096:
+            raise ValueError("step_hmc: nleap must lie in [1, 4096]")
+        if correlate and every < 1:
+            raise ValueError("step_hmc: correlate=True needs every >= 1")
+        ser = np.zeros((max(n, 0) // every, self.R, 4)) if every > 0 else None
+        rec = np.zeros((max(n, 0), self.R, 4)) if record else None
+        _lib.call("sq_phi4_ens_step_hmc", self._h, n, nleap, 1 if randomize else 0, every,
+                  _dptr(ser) if ser is not None and ser.size else None, 1 if correlate else 0,
+                  _dptr(rec) if rec is not None and rec.size else None)
+        return (ser, rec) if record else ser
+
+    def hmc_stats(self, first=0, count=None):
+        """(count, 4) int64: trajectories, accepted, rejected by the guard, and
+        leapfrog steps, per replica, since creation or `hmc_reset`
+        (sq_phi4_ens_hmc_stats).  The MALA counters are separate."""
+        k = self._count(first, count)
+        out = np.zeros((max(k, 0), 4), dtype=np.int64)
+        _lib.call("sq_phi4_ens_hmc_stats", self._h, int(first), k, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def hmc_reset(self, first=0, count=None):
+        """Clear the HMC counters of replicas first .. first + count."""
+        _lib.call("sq_phi4_ens_hmc_reset", self._h, int(first), self._count(first, count))
+
     def step_flow(self, n=1, every=1, correlate=False, scheme="euler"):
         """n steps of every replica in one launch, as `step`, with a flow
         measurement after each every-th step (every >= 1, `set_flow` first;
@@ -833,6 +898,7 @@ class Phi4Ensemble:
         those of `step(n, scheme=scheme)`.  `step(n, every=k, flow=True,
         correlate=...)` is this call with Euler steps; scheme="heun" is reached
         here only (`step` refuses it with flow=True)."""
+        _refuse_hmc(scheme, "step_flow")
         if scheme == "mala":
             raise ValueError("scheme='mala' does not run with the flow (use flowed() between calls)")
         if scheme not in ("euler", "heun"):
@@ -859,6 +925,7 @@ class Phi4Ensemble:
         nothing.  Verdicts, dtau, fields, counters, flags and the stability
         records are those of the call without the flow.  `run_frames(n,
         flow=True, ...)` is this call."""
+        _refuse_hmc(scheme, "run_frames_flow")
         if scheme == "mala":
             raise ValueError(_MALA_NO_FRAMES)
         if scheme not in ("euler", "heun"):
@@ -916,6 +983,7 @@ class Phi4Ensemble:
         flow accumulators.  momenta=True is refused with ValueError before any
         library call.  scheme="mala" is refused likewise: frames have no
         meaning under an accept/reject step."""
+        _refuse_hmc(scheme, "run_frames")
         if scheme == "mala":
             raise ValueError(_MALA_NO_FRAMES)
         if scheme not in ("euler", "heun"):
@@ -937,6 +1005,7 @@ class Phi4Ensemble:
 
     def run_frame(self, scheme="euler"):
         """One frame of every replica; (R,) bool: stable."""
+        _refuse_hmc(scheme, "run_frame")
         return self.run_frames(1, scheme=scheme)[0][0]
 
     @staticmethod
