@@ -145,6 +145,102 @@ def test_phi4_ens_heun_random_shapes(gpu, oracle_mod, bm_tables, shape, steps, e
                 (shape, info, r, C, step0, np.max(np.abs(got[r] - ref[r])))
 
 
+# MALA and HMC: the verdicts the oracle followed, per sampler and K
+_sampler_tally = {"mala": {}, "hmc": {}}
+_SAMPLER_FUZZ = dict(
+    shape=_ens_shapes(), seed=st.integers(0, 2 ** 40),
+    step0=st.tuples(st.integers(0, 2 ** 40), st.integers(0, 2 ** 40)).filter(lambda t: t[0] != t[1]),
+    m2=st.sampled_from([(0.5, -0.5), (1.0, 0.25)]), lam=st.sampled_from([(1.0, 2.0), (4.0, 0.5)]),
+    C=st.tuples(st.sampled_from([0.5, 0.7, 1.0]), st.sampled_from([0.5, 0.7, 1.0])),
+    # dtau = 0.4 / sqrt(V) x fac.  With factors of 0.5, 1 and 1.5 nine trajectories in ten are accepted and a K
+    # band of some 30 trajectories can go without a rejection (MALA at K = 2: one in two runs on an MI355X, none in a
+    # third); with these a CPU run of the same cases rejects 4 of 10 to 17 of 28 per band.
+    fac=st.tuples(st.sampled_from([2.0, 3.5, 5.0]), st.sampled_from([2.0, 3.5, 5.0])),
+    ntraj=st.integers(1, 4), every=st.integers(0, 2), correlate=st.booleans())
+
+
+def _sampler_case(o, sampler, shape, seed, step0, m2, lam, C, fac, ntraj, nleap, randomize, every, correlate):
+    """Two replicas with different dtau = 0.4 / sqrt(V) x fac, m2, lam, C, seeds and start counters, thermalised
+    with 60 Euler steps on the GPU; ntraj trajectories (MALA: nleap = 1) in one call or two; fields, records,
+    counters, counts and flags through test_gpu_phi4_ens_hmc.py's check_trajectories; the series rows within
+    2 n u sum |t| of the exactly rounded sums of the oracle's field at that point."""
+    from stochquant_amd import Phi4Ensemble
+    from test_gpu_phi4_ens import _exact_sums
+    from test_gpu_phi4_ens_hmc import check_trajectories
+    info = Phi4Ensemble.shape_info(shape)                  # raises if the strategy left the legal shapes
+    dtau = [0.4 / (shape[0] * shape[1] * shape[2]) ** 0.5 * f for f in fac]
+    seeds = [seed, seed + 12345]
+    correlate = correlate and every >= 1
+    calls = [ntraj] if ntraj == 1 else [ntraj // 2, ntraj - ntraj // 2]
+    with Phi4Ensemble(shape, 2, dtau=dtau, m2=m2, lam=lam, C=C, seeds=seeds) as E:
+        E.init_field(0.5)
+        E.step(60)
+        E.step_counter = list(step0)
+        start = E.download()
+        sers, recs, after = [], [], []
+        for n in calls:
+            if sampler == "hmc":
+                ser, rec = E.step_hmc(n, nleap=nleap, randomize=randomize, every=every, correlate=correlate, record=True)
+            else:
+                ser, rec = E.step_mala(n, every=every, correlate=correlate, record=True)
+                rec = np.concatenate([rec, np.ones((n, 2, 1))], axis=2)      # a trajectory of one step
+            assert (ser is None) if every == 0 else (ser.shape == (n // every, 2, 4))
+            sers.append(ser)
+            recs.append(rec)
+            after.append(E.download())
+        assert [int(s) for s in E.step_counter] == [s + ntraj for s in step0]
+        stats = E.hmc_stats() if sampler == "hmc" else E.mala_stats()
+        other = E.mala_stats() if sampler == "hmc" else E.hmc_stats()
+        flags, nmeas = E.flags(), E.corr_sums()[2]
+    assert not other.any()
+    assert list(nmeas) == [sum(n // every for n in calls) if correlate else 0] * 2
+    rec = np.concatenate(recs)
+    for r in range(2):
+        par = (dtau[r], m2[r], lam[r], C[r], seeds[r])
+        fields, verdicts, lengths = check_trajectories(o, shape, par, start[r], step0[r], rec[:, r], nleap, randomize)
+        done = 0
+        for n, ser, got in zip(calls, sers, after):
+            for i in range(n // every if every else 0):
+                exact, bound, _ = _exact_sums(fields[done + (i + 1) * every - 1])
+                err = np.abs(ser[i, r] - exact)
+                assert np.all(err <= bound), (shape, info, r, done, i, err, bound)
+            done += n
+            assert np.array_equal(got[r].view(np.uint32), fields[done - 1].view(np.uint32)), (shape, info, r, done)
+        want = [ntraj, verdicts.count(1), verdicts.count(2), sum(lengths)]
+        assert list(stats[r]) == (want if sampler == "hmc" else want[:3]), (shape, info, r, stats[r], verdicts, lengths)
+        assert bool(flags[r]) == (2 in verdicts), (shape, info, r, verdicts)
+        _sampler_tally[sampler].setdefault(info["K"], []).extend(verdicts)
+
+
+@settings(max_examples=30, deadline=None, derandomize=True,
+          suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
+@given(**_SAMPLER_FUZZ)
+def test_phi4_ens_mala_random_shapes(gpu, dev_oracle, shape, seed, step0, m2, lam, C, fac, ntraj, every, correlate):
+    """The ensemble's MALA step at random legal shapes over all four K (_sampler_case)."""
+    _sampler_case(dev_oracle, "mala", shape, seed, step0, m2, lam, C, fac, ntraj, 1, False, every, correlate)
+
+
+@settings(max_examples=30, deadline=None, derandomize=True,
+          suppress_health_check=[HealthCheck.function_scoped_fixture, HealthCheck.too_slow])
+@given(nleap=st.integers(1, 6), randomize=st.booleans(), **_SAMPLER_FUZZ)
+def test_phi4_ens_hmc_random_shapes(gpu, dev_oracle, shape, seed, step0, m2, lam, C, fac, ntraj, every, correlate, nleap,
+                                    randomize):
+    """The ensemble's HMC trajectories at random legal shapes over all four K, nleap = 1 .. 6 fixed or
+    randomised (_sampler_case)."""
+    _sampler_case(dev_oracle, "hmc", shape, seed, step0, m2, lam, C, fac, ntraj, nleap, randomize, every, correlate)
+
+
+def test_phi4_ens_sampler_fuzz_saw_both_verdicts(gpu):
+    """The two tests above followed accepted and rejected trajectories at every K.  (They run before this one:
+    pytest keeps the file's order.)"""
+    for sampler, tally in _sampler_tally.items():
+        assert set(tally) == {1, 2, 4, 8}, (sampler, sorted(tally))
+        for K, vs in sorted(tally.items()):
+            print(f"FUZZ {sampler} K = {K}: {len(vs)} trajectories, {vs.count(1)} accepted, {vs.count(0)} rejected, "
+                  f"{vs.count(2)} trips", flush=True)
+            assert {0, 1} <= set(vs), (sampler, K, vs)
+
+
 def _exact(res):
     for k in ("stable", "dtau", "lrgEl", "lrgVl", "omega", "runs", "seed"):
         assert res[k][0] == res[k][1], (res["frame"], k, res[k])

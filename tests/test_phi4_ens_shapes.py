@@ -59,9 +59,24 @@ GPU_SHAPES = {
 }
 
 
+# The shapes at which the MALA and HMC samplers measure in flight (test_gpu_phi4_ens_sampler_edges.py), one or
+# two of every class (K, images of the plain step launch, images of the step launch with the correlator): the
+# measuring kernels are instances of their own, and their image count follows the correlator's layout.
+SAMPLER_MEASURE_SHAPES = [(8, 8, 8), (8, 17, 31), (64, 16, 8), (16, 24, 24), (64, 3, 43), (32, 24, 24), (8, 50, 51),
+                          (64, 11, 29)]
+TWO_TO_ONE = (8, 50, 51)      # two images plain, one with the correlator's 8 Lz bytes
+
+
 def shape_info(shape):
     from stochquant_amd import Phi4Ensemble
     return Phi4Ensemble.shape_info(shape)
+
+
+def measure_class(shape, info=None):
+    """(K, images of the plain step launch, images of the step launch with the correlator)."""
+    from stochquant_amd import Phi4Ensemble
+    i = shape_info(shape) if info is None else info
+    return (i["K"], i["images"], Phi4Ensemble.corr_shape_info(shape)["images"])
 
 
 def shape_class(shape, info=None):
@@ -158,3 +173,20 @@ def test_gpu_shape_list_covers_every_class(infos):
         ", ".join(f"{n} = {v}" for n, v in zip(names, c)) + f" (e.g. {s[0]} x {s[1]} x {s[2]})"
         for c, s in sorted(missing.items()))
     assert {s[0] for s in GPU_SHAPES} == set(LX)
+
+
+def test_sampler_measure_list_covers_every_class(infos):
+    """The samplers' measuring instances: every (K, plain images, correlator images) that a legal shape has is in
+    SAMPLER_MEASURE_SHAPES, the correlator never adds an image, and TWO_TO_ONE is the class it takes one from."""
+    classes = {}
+    for s, i in infos.items():
+        classes.setdefault(measure_class(s, i), s)
+    assert set(classes) == {(1, 2, 2), (2, 2, 2), (4, 2, 2), (8, 2, 2), (8, 2, 1), (8, 1, 1)}, classes
+    have = {measure_class(s, infos[s]) for s in SAMPLER_MEASURE_SHAPES}
+    assert have == set(classes), {c: s for c, s in classes.items() if c not in have}
+    assert measure_class(TWO_TO_ONE, infos[TWO_TO_ONE]) == (8, 2, 1) and TWO_TO_ONE in SAMPLER_MEASURE_SHAPES
+    assert all(s in GPU_SHAPES for s in SAMPLER_MEASURE_SHAPES)
+    # missing quads (K T > Q) at K = 2, 4 and in all three K = 8 classes
+    missing = {measure_class(s, infos[s]) for s in SAMPLER_MEASURE_SHAPES
+               if infos[s]["K"] * infos[s]["T"] > s[0] * s[1] * s[2] // 4}
+    assert missing == {(2, 2, 2), (4, 2, 2), (8, 2, 1), (8, 1, 1)}, missing
