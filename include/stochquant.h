@@ -765,6 +765,96 @@ int sq_phi4_ens_step_hmc(sq_phi4_ens *e, int ntraj, int nleap, int randomize, in
 int sq_phi4_ens_hmc_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][4]*/);
 int sq_phi4_ens_hmc_reset(sq_phi4_ens *e, int first, int count);
 
+/* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
+ * replicas of a ladder swap their fields with a Metropolis test, decided and
+ * carried out on the device.  ABI 6: symbols added, none
+ * changed.
+ *
+ * Ladders.  sq_phi4_ens_set_ladder(e, nlad) cuts the R replicas into R / nlad
+ * ladders of nlad consecutive slots: 2 <= nlad <= R and R % nlad == 0, else
+ * SQ_E_ARG; nlad = 0 switches ladders off, the state at creation.  The rungs'
+ * parameters are whatever sq_phi4_ens_set_params gave the slots: the library
+ * neither orders nor checks them.  sq_phi4_ens_get_ladder returns nlad.
+ *
+ * Rounds.  The handle keeps a 64-bit exchange-round counter x, 0 at creation
+ * (sq_phi4_ens_exchange_round, sq_phi4_ens_set_exchange_round).  Round x pairs
+ * slots (l nlad + o + 2j, l nlad + o + 2j + 1), o = x & 1, for every ladder l
+ * and every j with both slots inside the ladder: pairs never cross a ladder
+ * boundary.  A round with no pair (nlad = 2, odd x) launches nothing.  x
+ * advances by one per round whatever happened.
+ *
+ * One pair (a, b = a + 1) holding phi_a, phi_b, with the slots' records
+ * (h = dtau, m2, lam6, sig, key) as in the MALA definition above.  Everything
+ * in double from the float records, no contraction:
+ *   S2, S4, NN of each field: sq_phi4_ens_moments' values bit for bit;
+ *   beta_r = 2 h_r / (sig_r sig_r), p_r = beta_r (3 + m2_r / 2),
+ *   q_r = beta_r (lam6_r / 4) for r = a, b: MALA's S and MALA's 2h / sig^2, so
+ *   the test is exact for the densities exp(-beta_r S_r) = exp(-S_r / C_r^2)
+ *   that sq_phi4_ens_step_mala and sq_phi4_ens_step_hmc sample;
+ *   Delta = (p_a - p_b)(S2_b - S2_a) - (beta_a - beta_b)(NN_b - NN_a) + (q_a - q_b)(S4_b - S4_a),
+ *   the three products summed left to right: E_a(phi_b) + E_b(phi_a) -
+ *   E_a(phi_a) - E_b(phi_b) with E_r = beta_r S_r;
+ *   u = (o.x + 0.5) 2^-32, o the Philox4x32-10 block at counter
+ *   {0, 4 << 24, x lo, x hi} under the key of slot a (stream 4);
+ *   verdict 1 if Delta <= 0 or u < exp(-Delta) (the device's double exp), else
+ *   0, a NaN Delta included.
+ * On verdict 1 row a of the field array gets phi_b and row b gets phi_a, bit for
+ * bit, and the two slots' walker labels change places; on verdict 0 no field
+ * word is written.  Parameters, keys, step counters, guard flags, frame state,
+ * every correlator, momentum and flow accumulator and the MALA / HMC counters
+ * are left alone in both cases: they belong to the slot, that is to the
+ * parameter set, as they do for sq_phi4_ens_upload.
+ *
+ * State per slot, in device memory: xstat[r] = {attempts, acceptances} of the
+ * pair (r, r + 1), zero at creation; walker[r], r at creation
+ * (sq_phi4_ens_exchange_stats, sq_phi4_ens_walkers; sq_phi4_ens_exchange_reset
+ * clears the counters of a range and, walkers != 0, sets its labels back to
+ * the slot index).
+ *
+ * Limits.  A replica with sig == 0 makes the exchange calls fail with
+ * SQ_E_STATE before anything is launched, as no ladder set does.  The test is
+ * meaningful only between equilibrium fields, fields drawn from
+ * exp(-beta_r S_r): after sq_phi4_ens_step_mala or sq_phi4_ens_step_hmc, or
+ * after Euler / Heun steps up to their dtau bias; exchanging fields that are
+ * still thermalising samples nothing in particular.
+ *
+ * sq_phi4_ens_exchange: nrounds consecutive rounds, enqueued back to back, one
+ * synchronisation at the end.  rec, nullable: [nrounds][nrep][5] = Delta, u,
+ * verdict, partner slot, the walker label the slot holds after the round; both
+ * slots of a pair carry the pair's Delta, u and verdict; a slot without a
+ * partner in that round has verdict -1, partner -1, Delta = u = 0.
+ *
+ * sq_phi4_ens_step_hmc_exchange: per round the sq_phi4_ens_step_hmc launch of
+ * ntraj trajectories, then one exchange round; all 2 nrounds launches on the
+ * handle's stream, one synchronisation at the end.  every > 0 needs
+ * ntraj % every == 0 (SQ_E_ARG), so that series ([nrounds ntraj / every][nrep][4])
+ * and the correlator measurements are those of the separate calls: a
+ * measurement sees the field a slot holds after its trajectory and before the
+ * round's exchange.  rec_hmc: [nrounds ntraj][nrep][4], rec_x as rec above, both
+ * nullable.  The call is bit for bit the loop { sq_phi4_ens_step_hmc(ntraj, ..);
+ * sq_phi4_ens_exchange(1, ..) } in fields, series, records, accumulators,
+ * counters, flags, statistics and walkers.  nleap = 1 serves MALA.
+ * sq_phi4_ens_perf counts one step per trajectory and every launch.
+ *
+ * sq_phi4_ens_exchange_shape_info: out = {K, T, LDS bytes, LDS limit} of the
+ * exchange launch (one work-group per pair, the moments launch's shape); needs
+ * no device; SQ_E_ARG for the shapes sq_phi4_ens_create refuses.
+ * All argument and state checks come before any device work; nrounds = 0 does
+ * nothing after them. */
+int sq_phi4_ens_set_ladder(sq_phi4_ens *e, int nlad);
+int sq_phi4_ens_get_ladder(sq_phi4_ens *e, int *nlad);
+int sq_phi4_ens_exchange_round(sq_phi4_ens *e, unsigned long long *x);
+int sq_phi4_ens_set_exchange_round(sq_phi4_ens *e, unsigned long long x);
+int sq_phi4_ens_exchange(sq_phi4_ens *e, int nrounds, double *rec /*[nrounds][R][5], nullable*/);
+int sq_phi4_ens_step_hmc_exchange(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                  double *series /*[nrounds ntraj/every][R][4]*/, int measure /*bit 0: correlate*/,
+                                  double *rec_hmc /*[nrounds ntraj][R][4], nullable*/,
+                                  double *rec_x /*[nrounds][R][5], nullable*/);
+int sq_phi4_ens_exchange_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][2]*/);
+int sq_phi4_ens_walkers(sq_phi4_ens *e, int first, int count, int *out /*[count]*/);
+int sq_phi4_ens_exchange_reset(sq_phi4_ens *e, int first, int count, int walkers);
+int sq_phi4_ens_exchange_shape_info(const int dims[3], int out[4]);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

@@ -229,6 +229,17 @@ SIGNATURES = {
     "sq_phi4_ens_step_hmc": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
     "sq_phi4_ens_hmc_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ens_hmc_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_set_ladder": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sq_phi4_ens_get_ladder": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_exchange_round": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "sq_phi4_ens_set_exchange_round": (ctypes.c_int, [_P, ctypes.c_ulonglong]),
+    "sq_phi4_ens_exchange": (ctypes.c_int, [_P, ctypes.c_int, _D]),
+    "sq_phi4_ens_step_hmc_exchange": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     _D, ctypes.c_int, _D, _D]),
+    "sq_phi4_ens_exchange_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ens_walkers": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_exchange_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_exchange_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4

@@ -70,6 +70,13 @@ struct sq_phi4_ens {
                                          // (first HMC call on); cleared by sq_phi4_ens_hmc_reset only
     double *hrec = nullptr;              // the last HMC call's per-trajectory records: pinned host memory
     size_t hrec_cap = 0;                 // ... in doubles
+    int nlad = 0;                        // slots per exchange ladder (sq_phi4_ens_set_ladder), 0: no ladders
+    unsigned long long xround = 0;       // the exchange-round counter
+    long long *xstat = nullptr;          // [R][2] attempts, acceptances of the pair (r, r + 1); zero at creation,
+                                         // cleared by sq_phi4_ens_exchange_reset only
+    int *walker = nullptr;               // [R] the label of the field each slot holds; r at creation
+    double *xrec = nullptr;              // the last exchange call's records: pinned host memory the kernel writes
+    size_t xrec_cap = 0;                 // ... in doubles
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -179,6 +186,13 @@ void release_phi4_ens(sq_phi4_ens *e) {
     e->hstat = nullptr;
     e->hrec = nullptr;
     e->hrec_cap = 0;
+    (void)hipFree(e->xstat);
+    (void)hipFree(e->walker);
+    (void)hipHostFree(e->xrec);
+    e->xstat = nullptr;
+    e->walker = nullptr;
+    e->xrec = nullptr;
+    e->xrec_cap = 0;
     e->frec = nullptr;
     e->fG = e->fS1 = e->ftmp = nullptr;
     e->fN = nullptr;
@@ -315,6 +329,14 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         SQ_HIP(hipMemset(e->cN, 0, sizeof(long long) * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->pN, sizeof(long long) * (size_t)nrep));
         SQ_HIP(hipMemset(e->pN, 0, sizeof(long long) * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->xstat, sizeof(long long) * 2 * (size_t)nrep));
+        SQ_HIP(hipMemset(e->xstat, 0, sizeof(long long) * 2 * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->walker, sizeof(int) * (size_t)nrep));
+        {
+            std::vector<int> id((size_t)nrep);
+            for (int r = 0; r < nrep; ++r) id[(size_t)r] = r;
+            SQ_HIP(hipMemcpy(e->walker, id.data(), sizeof(int) * (size_t)nrep, hipMemcpyHostToDevice));
+        }
         SQ_HIP(hipMemset(e->field, 0, bytes));
         SQ_HIP(hipMemset(e->flags, 0, sizeof(int) * (size_t)nrep));
         SQ_HIP(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
@@ -1420,6 +1442,250 @@ int sq_phi4_ens_hmc_reset(sq_phi4_ens *e, int first, int count) {
     DeviceGuard g(e->dev);
     SQ_HIP(hipMemset(e->hstat + 4 * (size_t)first, 0, sizeof(long long) * 4 * (size_t)count));
     SQ_HIP(hipDeviceSynchronize());
+    return SQ_OK;
+}
+
+}  // extern "C"
+
+// ---- replica exchange (sq_phi4_ens_exchange.hip) ----
+namespace {
+
+// A pinned host buffer of at least n doubles (the kernels write their records there, as ens_step's series).
+int ens_pinned(double *&buf, size_t &cap, size_t n) {
+    if (n <= cap) return SQ_OK;
+    (void)hipHostFree(buf);
+    buf = nullptr;
+    cap = 0;
+    SQ_HIP(hipHostMalloc(&buf, sizeof(double) * n, hipHostMallocDefault));
+    cap = n;
+    return SQ_OK;
+}
+
+// What stands against an exchange round, checked before any device work.
+int ens_xchg_state(const sq_phi4_ens *e) {
+    if (e->nlad == 0)
+        return fail(SQ_E_STATE, "an exchange round needs ladders: call sq_phi4_ens_set_ladder first");
+    for (int r = 0; r < e->R; ++r)
+        if (ens_rec(e->rep[(size_t)r]).sig == 0.0f)
+            return fail(SQ_E_STATE, "an exchange round needs C != 0 in every replica (sig = sqrt(2 dtau) C is zero in "
+                                    "fp32): beta = 2 dtau / sig^2 has no value");
+    return SQ_OK;
+}
+
+// Enqueue round e->xround + i; rec: the round's [R][5] rows in pinned memory, nullable.
+int ens_xchg_enqueue(sq_phi4_ens *e, int i, double *rec) {
+    sq::Phi4EnsXchgArgs w{};
+    w.stat = e->xstat;
+    w.walker = e->walker;
+    w.rec = rec;
+    w.nlad = e->nlad;
+    w.x = e->xround + (unsigned long long)i;
+    if (sq::phi4_ens_xchg_pairs(w.nlad, w.x) == 0) return SQ_OK;  // nothing to launch
+    SQ_HIP(sq::phi4_ens_exchange_launch(ens_args(e), w, e->R, e->stream));
+    e->launches++;
+    return SQ_OK;
+}
+
+// The rows of the slots without a partner, round by round behind the synchronisation: verdict -1, partner -1,
+// Delta = u = 0 and the label the slot held before the round (lab: the labels at the call's start, updated here).
+void ens_xchg_fill(const sq_phi4_ens *e, int nrounds, double *rec, std::vector<int> &lab) {
+    for (int i = 0; i < nrounds; ++i) {
+        const unsigned long long x = e->xround + (unsigned long long)i;
+        const int o = (int)(x & 1ull), np = sq::phi4_ens_xchg_pairs(e->nlad, x);
+        for (int r = 0; r < e->R; ++r) {
+            double *row = rec + 5 * ((size_t)i * (size_t)e->R + (size_t)r);
+            const int pos = r % e->nlad;
+            if (pos >= o && pos - o < 2 * np) {
+                lab[(size_t)r] = (int)row[4];
+            } else {
+                row[0] = row[1] = 0.0;
+                row[2] = row[3] = -1.0;
+                row[4] = (double)lab[(size_t)r];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_set_ladder(sq_phi4_ens *e, int nlad) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nlad != 0 && (nlad < 2 || nlad > e->R || e->R % nlad != 0))
+        return fail(SQ_E_ARG, "nlad must be 0 (no ladders) or lie in [2, nrep] and divide nrep");
+    e->nlad = nlad;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_get_ladder(sq_phi4_ens *e, int *nlad) {
+    if (!e || !nlad) return fail(SQ_E_ARG, "null argument");
+    *nlad = e->nlad;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_exchange_round(sq_phi4_ens *e, unsigned long long *x) {
+    if (!e || !x) return fail(SQ_E_ARG, "null argument");
+    *x = e->xround;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_set_exchange_round(sq_phi4_ens *e, unsigned long long x) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    e->xround = x;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_exchange(sq_phi4_ens *e, int nrounds, double *rec) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nrounds < 0) return fail(SQ_E_ARG, "nrounds must be >= 0");
+    int rc = ens_xchg_state(e);
+    if (rc) return rc;
+    if (nrounds == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    rc = ens_sync_recs(e);
+    if (rc) return rc;
+    const size_t nx = rec ? (size_t)nrounds * (size_t)e->R * 5 : 0;
+    rc = ens_pinned(e->xrec, e->xrec_cap, nx);
+    if (rc) return rc;
+    std::vector<int> lab;
+    if (nx) {
+        lab.resize((size_t)e->R);
+        SQ_HIP(hipMemcpy(lab.data(), e->walker, sizeof(int) * (size_t)e->R, hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < nrounds; ++i) {
+        rc = ens_xchg_enqueue(e, i, nx ? e->xrec + 5 * (size_t)i * (size_t)e->R : nullptr);
+        if (rc) break;
+    }
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (rc) return rc;
+    SQ_HIP(he);
+    if (nx) {
+        ens_xchg_fill(e, nrounds, e->xrec, lab);
+        memcpy(rec, e->xrec, sizeof(double) * nx);
+    }
+    e->xround += (unsigned long long)nrounds;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_step_hmc_exchange(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                  double *series, int measure, double *rec_hmc, double *rec_x) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nrounds < 0) return fail(SQ_E_ARG, "nrounds must be >= 0");
+    if (ntraj < 0) return fail(SQ_E_ARG, "ntraj must be >= 0");
+    if (nleap < 1 || nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap must lie in [1, 4096]");
+    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a trajectory measures no momenta");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
+    if (every > 0 && ntraj % every != 0)
+        return fail(SQ_E_ARG, "every must divide ntraj: the measurements are those of the separate calls");
+    int rc = ens_xchg_state(e);  // the trajectories' C != 0 as well
+    if (rc) return rc;
+    if (nrounds == 0) return SQ_OK;
+    const bool corr = (measure & 1) != 0;
+    DeviceGuard g(e->dev);
+    rc = ens_sync_recs(e);
+    if (rc) return rc;
+    rc = ens_hmc_stat(e);
+    if (rc) return rc;
+    const size_t per = (every > 0 && series) ? (size_t)(ntraj / every) * (size_t)e->R * 4 : 0;  // a round's series
+    const size_t nd = per * (size_t)nrounds;
+    const size_t perh = rec_hmc ? (size_t)ntraj * (size_t)e->R * 4 : 0;
+    const size_t nm = perh * (size_t)nrounds;
+    const size_t nx = rec_x ? (size_t)nrounds * (size_t)e->R * 5 : 0;
+    rc = ens_pinned(e->series, e->series_cap, nd);
+    if (rc) return rc;
+    rc = ens_pinned(e->hrec, e->hrec_cap, nm);
+    if (rc) return rc;
+    rc = ens_pinned(e->xrec, e->xrec_cap, nx);
+    if (rc) return rc;
+    std::vector<int> lab;
+    if (nx) {
+        lab.resize((size_t)e->R);
+        SQ_HIP(hipMemcpy(lab.data(), e->walker, sizeof(int) * (size_t)e->R, hipMemcpyDeviceToHost));
+    }
+    sq::Phi4EnsHmcArgs w{};
+    w.stat = e->hstat;
+    w.nleap = nleap;
+    w.randomize = randomize != 0 ? 1 : 0;
+    const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+    for (int i = 0; i < nrounds && !rc; ++i) {
+        if (ntraj > 0) {
+            sq::Phi4EnsArgs a = ens_args(e);
+            a.adv = e->adv + (unsigned long long)i * (unsigned long long)ntraj;
+            a.nsteps = ntraj;
+            a.every = (nd || corr) ? every : 0;
+            a.series = nd ? e->series + per * (size_t)i : nullptr;
+            w.rec = nm ? e->hrec + perh * (size_t)i : nullptr;
+            const hipError_t he = sq::phi4_ens_hmc_launch(a, w, corr ? &c : nullptr, e->R, e->stream);
+            if (he != hipSuccess) {
+                rc = fail(SQ_E_HIP, std::string("phi4_ens_hmc_launch: ") + hipGetErrorString(he));
+                break;
+            }
+            e->launches++;
+        }
+        rc = ens_xchg_enqueue(e, i, nx ? e->xrec + 5 * (size_t)i * (size_t)e->R : nullptr);
+    }
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (rc) return rc;
+    SQ_HIP(he);
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    if (nm) memcpy(rec_hmc, e->hrec, sizeof(double) * nm);
+    if (nx) {
+        ens_xchg_fill(e, nrounds, e->xrec, lab);
+        memcpy(rec_x, e->xrec, sizeof(double) * nx);
+    }
+    const unsigned long long tot = (unsigned long long)nrounds * (unsigned long long)ntraj;
+    e->adv += tot;  // one count per trajectory
+    for (auto &r : e->rep) r.step += tot;
+    e->steps_total += (long long)tot * e->R;
+    e->xround += (unsigned long long)nrounds;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_exchange_stats(sq_phi4_ens *e, int first, int count, long long *out) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!out) return fail(SQ_E_ARG, "null argument");
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemcpy(out, e->xstat + 2 * (size_t)first, sizeof(long long) * 2 * (size_t)count, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_walkers(sq_phi4_ens *e, int first, int count, int *out) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!out) return fail(SQ_E_ARG, "null argument");
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemcpy(out, e->walker + first, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_exchange_reset(sq_phi4_ens *e, int first, int count, int walkers) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemset(e->xstat + 2 * (size_t)first, 0, sizeof(long long) * 2 * (size_t)count));
+    if (walkers) {
+        std::vector<int> id((size_t)count);
+        for (int r = 0; r < count; ++r) id[(size_t)r] = first + r;
+        SQ_HIP(hipMemcpy(e->walker + first, id.data(), sizeof(int) * (size_t)count, hipMemcpyHostToDevice));
+    }
+    SQ_HIP(hipDeviceSynchronize());
+    return SQ_OK;
+}
+
+int sq_phi4_ens_exchange_shape_info(const int dims[3], int out[4]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
+    out[0] = s.K;
+    out[1] = s.T;
+    out[2] = s.mom_lds_bytes;
+    out[3] = sq::kPhi4EnsLdsBytes;
     return SQ_OK;
 }
 

@@ -281,4 +281,26 @@ hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, d
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.
 hipError_t phi4_ens_init_launch(const Phi4EnsArgs &a, int nrep, float amp, hipStream_t s);
 
+// ---- replica exchange (sq_phi4_ens_exchange.hip) ----
+// The Philox stream of the pair test's uniform: counter {0, kPhi4EnsStreamExchange << 24, x lo, x hi} under the
+// key of the pair's lower slot.  The fifth stream, behind the four of sq_noise_consts.h.
+constexpr uint32_t kPhi4EnsStreamExchange = 4;
+
+// One exchange round: the ladders, the round's counter, the slots' counters and labels, the optional record.
+struct Phi4EnsXchgArgs {
+    long long *stat;       // [R][2] = attempts, acceptances of the pair (r, r + 1), at r (device memory)
+    int *walker;           // [R] the label of the field each slot holds (device memory)
+    double *rec;           // [R][5] = Delta, u, verdict, partner, walker after the round: the rows of paired slots
+                           // only, device-visible (pinned host memory); nullable
+    int nlad;              // slots per ladder, >= 2, divides nrep
+    unsigned long long x;  // the round: pairs (l nlad + o + 2 j, + 1), o = x & 1
+};
+// Pairs of one ladder of nlad slots in round x: (nlad - (x & 1)) / 2.
+inline int phi4_ens_xchg_pairs(int nlad, unsigned long long x) { return (nlad - (int)(x & 1ull)) / 2; }
+// Round w.x of every ladder in one launch (phi4_ens_exchange_kernel): one work-group per pair, the moments
+// launch's work-group shape and LDS layout.  Both rows of a pair are read and written by that work-group alone.
+// Every replica's sig must be non-zero (the caller checks: the kernel divides by sig^2).  A round without a pair
+// launches nothing and is hipSuccess.  a.flags, a.series, a.nsteps, a.every, a.adv are not used.
+hipError_t phi4_ens_exchange_launch(const Phi4EnsArgs &a, const Phi4EnsXchgArgs &w, int nrep, hipStream_t s);
+
 }  // namespace sq

@@ -886,6 +886,112 @@ class Phi4Ensemble:
         """Clear the HMC counters of replicas first .. first + count."""
         _lib.call("sq_phi4_ens_hmc_reset", self._h, int(first), self._count(first, count))
 
+    def set_ladder(self, n):
+        """Cut the R replicas into R // n exchange ladders of n consecutive
+        slots (sq_phi4_ens_set_ladder): 2 <= n <= R and R % n == 0; n = 0
+        switches ladders off, the state at creation.  The rungs' parameters are
+        what `set_params` gave the slots -- typically a ladder in C; the library
+        neither orders nor checks them."""
+        _lib.call("sq_phi4_ens_set_ladder", self._h, int(n))
+
+    @property
+    def ladder(self):
+        n = ctypes.c_int(0)
+        _lib.call("sq_phi4_ens_get_ladder", self._h, ctypes.byref(n))
+        return n.value
+
+    @property
+    def exchange_round(self):
+        x = ctypes.c_ulonglong(0)
+        _lib.call("sq_phi4_ens_exchange_round", self._h, ctypes.byref(x))
+        return x.value
+
+    @exchange_round.setter
+    def exchange_round(self, v):
+        _lib.call("sq_phi4_ens_set_exchange_round", self._h, ctypes.c_ulonglong(int(v)))
+
+    def exchange(self, rounds=1, record=False):
+        """`rounds` replica-exchange rounds on the device, back to back
+        (sq_phi4_ens_exchange; include/stochquant.h has the definition).  Round
+        x pairs slots (l n + o + 2j, + 1), o = x & 1, inside every ladder; per
+        pair one work-group forms Δ = E_a(φ_b) + E_b(φ_a) - E_a(φ_a) - E_b(φ_b),
+        E_r = S_r / C_r², in double from the fields' sums, accepts when Δ <= 0
+        or u < exp(-Δ), and on acceptance swaps the two rows of the field array
+        and the two walker labels.  Parameters, counters, flags and every
+        accumulator stay with the slot.  `exchange_round` advances by one per
+        round.  record=True: returns the (rounds, R, 5) array of (Δ, u, verdict,
+        partner, walker after the round); a slot without a partner in a round
+        has verdict -1, partner -1.
+
+        Needs `set_ladder` and C != 0 in every replica (StochQuantError
+        otherwise).  The test is meaningful between equilibrium fields only:
+        after `step_mala` / `step_hmc`, or Euler / Heun steps up to their Δτ
+        bias."""
+        rounds = int(rounds)
+        rec = np.zeros((max(rounds, 0), self.R, 5)) if record else None
+        _lib.call("sq_phi4_ens_exchange", self._h, rounds, _dptr(rec) if rec is not None and rec.size else None)
+        return rec
+
+    def step_hmc_exchange(self, rounds, ntraj=1, nleap=1, randomize=False, every=0, correlate=False, record=False):
+        """`rounds` times: `step_hmc(ntraj, nleap, randomize, every, correlate)`,
+        then one `exchange` round -- all launches enqueued back to back with one
+        synchronisation at the end (sq_phi4_ens_step_hmc_exchange).  Bit for bit
+        the loop of the separate calls in everything.  every = k > 0 needs
+        ntraj % k == 0 and returns the (rounds * ntraj // k, R, 4) sums, taken
+        of the field a slot holds after its trajectory and before the round's
+        exchange; else None.  record=True: returns (series, rec_hmc, rec_x),
+        the (rounds * ntraj, R, 4) trajectory records of `step_hmc` and the
+        (rounds, R, 5) records of `exchange`.  nleap=1 is MALA with exchange."""
+        rounds, ntraj, nleap, every = int(rounds), int(ntraj), int(nleap), int(every)
+        if nleap < 1 or nleap > 4096:
+            raise ValueError("step_hmc_exchange: nleap must lie in [1, 4096]")
+        if correlate and every < 1:
+            raise ValueError("step_hmc_exchange: correlate=True needs every >= 1")
+        if every > 0 and ntraj % every != 0:
+            raise ValueError("step_hmc_exchange: every must divide ntraj")
+        nr, nj = max(rounds, 0), max(ntraj, 0)
+        ser = np.zeros((nr * (nj // every), self.R, 4)) if every > 0 else None
+        rh = np.zeros((nr * nj, self.R, 4)) if record else None
+        rx = np.zeros((nr, self.R, 5)) if record else None
+        _lib.call("sq_phi4_ens_step_hmc_exchange", self._h, rounds, ntraj, nleap, 1 if randomize else 0, every,
+                  _dptr(ser) if ser is not None and ser.size else None, 1 if correlate else 0,
+                  _dptr(rh) if rh is not None and rh.size else None,
+                  _dptr(rx) if rx is not None and rx.size else None)
+        return (ser, rh, rx) if record else ser
+
+    def exchange_stats(self, first=0, count=None):
+        """(count, 2) int64: attempts and acceptances of the pair (r, r + 1),
+        stored at r, since creation or `exchange_reset`
+        (sq_phi4_ens_exchange_stats)."""
+        k = self._count(first, count)
+        out = np.zeros((max(k, 0), 2), dtype=np.int64)
+        _lib.call("sq_phi4_ens_exchange_stats", self._h, int(first), k,
+                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def walkers(self, first=0, count=None):
+        """(count,) int32: the walker label each slot holds -- the slot its
+        field started in, carried along by every accepted exchange."""
+        k = self._count(first, count)
+        out = np.zeros(max(k, 0), dtype=np.int32)
+        _lib.call("sq_phi4_ens_walkers", self._h, int(first), k, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return out
+
+    def exchange_reset(self, first=0, count=None, walkers=False):
+        """Clear the exchange counters of replicas first .. first + count;
+        walkers=True also sets their labels back to the slot index."""
+        _lib.call("sq_phi4_ens_exchange_reset", self._h, int(first), self._count(first, count), 1 if walkers else 0)
+
+    @staticmethod
+    def exchange_shape_info(shape):
+        """What the exchange launch asks for, without a device: K quads per
+        lane, T lanes, dynamic LDS bytes and the LDS limit -- the moments
+        launch's shape, one work-group per pair."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 4)()
+        _lib.call("sq_phi4_ens_exchange_shape_info", dims, out)
+        return dict(zip(("K", "T", "lds_bytes", "lds_limit"), (int(v) for v in out)))
+
     def step_flow(self, n=1, every=1, correlate=False, scheme="euler"):
         """n steps of every replica in one launch, as `step`, with a flow
         measurement after each every-th step (every >= 1, `set_flow` first;
