@@ -73,7 +73,11 @@ def lib():
         L.orc_xcl.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int]
         L.orc_intconst.restype = ctypes.c_double
         L.orc_intconst.argtypes = [ctypes.c_int]
-        L.orc_qm1d_frame.argtypes = [ctypes.POINTER(Qm1d)]
+        L.orc_ddpot.restype = ctypes.c_double
+        L.orc_ddpot.argtypes = [ctypes.c_double, ctypes.c_int]
+        L.orc_ref_random.restype = ctypes.c_double
+        L.orc_ref_random.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+        L.orc_qm1d_frame.argtypes =[ctypes.POINTER(Qm1d)]
         L.orc_serial_launch.argtypes = [ctypes.POINTER(SerialDev)]
         L.orc_ref_noise_stream.argtypes = [ctypes.c_uint64, ctypes.c_int, ctypes.c_int, _D, _U32, _U32,
                                            ctypes.POINTER(ctypes.c_uint64)]
@@ -299,3 +303,99 @@ def tauhost(argv, cwd):
     if not os.path.exists(CLI):
         build()
     return subprocess.run([CLI] + [str(a) for a in argv], cwd=cwd, capture_output=True, timeout=300)
+
+
+# ---------------------------------------------------------------------------
+# One time_dev launch as data, and the reference's own compiled code
+# (oracle/_ref/, built by oracle/ref/Makefile where the reference's sources
+# exist; never present in a checkout, never read on the GPU box).
+# ---------------------------------------------------------------------------
+REF_DIR = os.path.join(HERE, "_ref")
+REF_LIB = os.path.join(REF_DIR, "libref_kernel.so")
+REF_CLI = os.path.join(REF_DIR, "tauhost_ref")
+_ARRAYS = ("f", "x", "xx0", "nf", "nx", "nxx0")
+
+
+def _launch_buffers(case):
+    """The six device arrays of a launch: f, x, xx0 as given, new* = their
+    copies (what tauhost.c:177-183 uploads before the first frame)."""
+    N = case["N"]
+    b = {k: np.array(case[k], dtype=np.float64) for k in ("f", "x", "xx0")}
+    assert all(v.shape == (N,) for v in b.values())
+    b.update({"n" + k: b[k].copy() for k in ("f", "x", "xx0")})
+    return b
+
+
+def _launch_result(b, omega, seed, stable, lrgEl, lrgVl):
+    out = {k: b[k] for k in _ARRAYS}
+    out.update(omega=float(omega), seed=int(seed), stable=int(stable), lrgEl=int(lrgEl), lrgVl=float(lrgVl))
+    return out
+
+
+def serial_launch(case):
+    """orc_serial_launch on a launch given as a dict (N, dt, dtau, pot, C,
+    loops, seed, omega, lrgEl, lrgVl, runs and the arrays f, x, xx0): every
+    output buffer and scalar."""
+    b = _launch_buffers(case)
+    d = SerialDev(N=case["N"], pot=case["pot"], loops=case["loops"], a=case["dt"], c=case["C"],
+                  omega=case["omega"], seed=case["seed"], stable=1, dtau=case["dtau"], lrgEl=case["lrgEl"],
+                  lrgVl=case["lrgVl"], runs=case["runs"])
+    for k in _ARRAYS:
+        setattr(d, k, b[k].ctypes.data_as(_D))
+    lib().orc_serial_launch(ctypes.byref(d))
+    return _launch_result(b, d.omega, d.seed, d.stable, d.lrgEl, d.lrgVl)
+
+
+def ref_available():
+    return os.path.exists(REF_LIB) and os.path.exists(REF_CLI)
+
+
+_ref = None
+
+
+def ref_lib():
+    """oracle/_ref/libref_kernel.so: the reference's kernel compiled as C
+    (helpers under their renamed symbols k_clas, k_ddPot, k_intConst, its
+    random() as cl_random) and ref_launch."""
+    global _ref
+    if _ref is None:
+        L = ctypes.CDLL(REF_LIB)
+        L.ref_launch.restype = ctypes.c_int
+        L.ref_launch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]
+        L.cl_random.restype = ctypes.c_double
+        L.cl_random.argtypes = [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+        L.k_clas.restype = ctypes.c_double
+        L.k_clas.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int]
+        L.k_ddPot.restype = ctypes.c_double
+        L.k_ddPot.argtypes = [ctypes.c_double, ctypes.c_int]
+        L.k_intConst.restype = ctypes.c_double
+        L.k_intConst.argtypes = [ctypes.c_int]
+        _ref = L
+    return _ref
+
+
+def ref_launch(case):
+    """The same launch through the reference's time_dev: global size N + 1,
+    one work-group, work-items in id order between barriers."""
+    b = _launch_buffers(case)
+    N = case["N"]
+    omega, dtau, lrgVl = (ctypes.c_double(case[k]) for k in ("omega", "dtau", "lrgVl"))
+    dt, C = ctypes.c_double(case["dt"]), ctypes.c_double(case["C"])
+    seed = ctypes.c_uint64(case["seed"])
+    stable, lrgEl, init_run = ctypes.c_int(1), ctypes.c_int(case["lrgEl"]), ctypes.c_int(1)
+    n, runs, pot, loops = (ctypes.c_int(case[k]) for k in ("N", "runs", "pot", "loops"))
+    scalars = [omega, seed, stable, dtau, lrgEl, lrgVl, init_run, n, dt, runs, pot, C, loops]
+    ptrs = [b[k].ctypes.data for k in _ARRAYS] + [ctypes.addressof(s) for s in scalars]
+    args = (ctypes.c_void_p * 19)(*ptrs)
+    if ref_lib().ref_launch(args, N + 1, N + 1) != 0:
+        raise RuntimeError("ref_launch")
+    return _launch_result(b, omega.value, seed.value, stable.value, lrgEl.value, lrgVl.value)
+
+
+def ref_tauhost(argv, cwd):
+    """The reference's host program on the stand-in runtime.  It opens
+    tau_kernel.cl in its working directory and the stand-in ignores what it
+    reads, so an empty file of that name is all it needs."""
+    with open(os.path.join(cwd, "tau_kernel.cl"), "a"):
+        pass
+    return subprocess.run([REF_CLI] + [str(a) for a in argv], cwd=cwd, capture_output=True, timeout=300)

@@ -11,9 +11,10 @@
  *  1. "serial" QM1D  -- the reference's exact semantics under a serialising
  *     OpenCL runtime (work-items 0..N in id order between barriers, one shared
  *     48-bit LCG), restating tau_kernel.cl:25-175 + :184-284 and the host
- *     frame loop tauhost.c:29-581.  Pinned against the only reference outputs
- *     that exist (recorded during the survey from the
- *     reference's unmodified sources); see tests/golden/README.md.
+ *     frame loop tauhost.c:29-581.  Pinned bit for bit to the reference's own
+ *     compiled code (oracle/ref/ -> oracle/_ref/, tests/test_reference_parity.py)
+ *     and to the launches and runs recorded from it (tests/golden/README.md);
+ *     the work-item schedule, one work-group in id order, is this project's.
  *
  *  2. "jacobi" QM1D  -- the same update with Jacobi ordering, counter-based
  *     Philox4x32-10 noise and an order-independent statement of the stability

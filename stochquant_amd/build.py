@@ -141,7 +141,25 @@ def build_oracle(verbose=False):
         raise RuntimeError("oracle build failed:\n" + r.stdout + r.stderr)
     if verbose:
         print(r.stdout)
+    build_reference(verbose=verbose)
     return os.path.join(odir, "liboracle.so")
+
+
+def build_reference(verbose=False):
+    """Where the reference's sources exist (SQ_REFERENCE_DIR, default
+    /root/reference), compile them unmodified into oracle/_ref/ by the recipe of
+    oracle/ref/Makefile, for the differential tests of
+    tests/test_reference_parity.py.  Nothing happens where they do not exist."""
+    ref = os.environ.get("SQ_REFERENCE_DIR", "/root/reference")
+    if not (os.path.isfile(os.path.join(ref, "tau_kernel.cl")) and os.path.isfile(os.path.join(ref, "tauhost.c"))):
+        return None
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle", "ref"), f"REF={os.path.abspath(ref)}"],
+                       capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError("reference build failed:\n" + r.stdout + r.stderr)
+    if verbose:
+        print(r.stdout)
+    return os.path.join(ROOT, "oracle", "_ref")
 
 
 def main(argv=None):

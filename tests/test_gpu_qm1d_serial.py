@@ -12,9 +12,17 @@ orc_serial_launch, pinned bit-exact to the reference's recorded outputs).
     consumed -- potID 3's x_cl = eta tanhf(...) included (glibc's tanhf,
     restated the same way; the hardware's differs by 1 ulp in ~14 % of
     arguments).
+  * Every launch of tests/golden/reference_launches.json, recorded from the
+    reference's own compiled kernel: potID 0 and 3 at the guard, from NaN and
+    infinite sites, with omega reflecting at either end or starting outside
+    [0, (N-1) dt], with lrgEl / lrgVl and running means carried in, frames
+    that break in the first round or later.
 """
 import numpy as np
 import pytest
+
+import reference_cases as rc
+from conftest import golden
 
 pytestmark = pytest.mark.gpu
 
@@ -138,40 +146,13 @@ def test_lcg_exceptional_calls(gpu, sqlib, oracle_mod, generator):
     """Seeds that drive the rare branches of random(): case P (s < 2^31 and
     t2 < 2^31 -> s + t2) and the u64 wrap of t2 - 2^31.  The parallel-prefix
     generator's exact fix-up must reproduce the serial chain bit for bit."""
-    M = (1 << 48) - 1
-    A, B = 0x5DEECE66D, 0xB
-    found = []
-    # search small seeds whose first call has t2 < 2^31 (case P from a small seed)
-    for s in range(1, 3_000_000):
-        t1 = ((s + 0) * A + B) & M
-        t2 = ((t1 + 0) * A + B) & M
-        if t2 < 2 ** 31:
-            found.append(s)
-            if len(found) == 2:
-                break
-    assert found
+    found = rc.case_p_first_call_seeds()
+    assert found and all(rc.lcg_pair(s, 0)[1] < 2 ** 31 for s in found)
     for seed in found:
         xi, w1, w2, seeds = _gpu_lcg(sqlib, seed, 7, 300, generator)
         rxi, rw1, rw2, rseeds = oracle_mod.ref_noise_stream(seed, 7, 300)
         assert np.array_equal(w1, rw1) and np.array_equal(w2, rw2) and np.array_equal(seeds, rseeds)
         assert np.array_equal(xi, rxi)
-
-
-_M48 = (1 << 48) - 1
-_A, _B = 0x5DEECE66D, 0xB
-
-
-def _seed_reaching(s_k, k, N):
-    """The seed whose case-Q chain (s' = A^2 s + beta(g), the common branch of
-    tau_kernel.cl:269-284) is s_k before call k: the chain run backwards."""
-    alpha = _A * _A & _M48
-    ainv = pow(alpha, -1, 1 << 48)
-    s = s_k
-    for j in range(k - 1, -1, -1):
-        g = j % (N + 1)
-        beta = (_A * _A * g + _A * _B + _A * g + _B - 2 ** 31) & _M48
-        s = ainv * (s - beta) & _M48
-    return s
 
 
 @pytest.mark.parametrize("kind,k", [("retry", 500_123), ("retry", 16_000), ("retry", 999_999),
@@ -184,15 +165,47 @@ def test_lcg_exception_mid_stream(gpu, sqlib, oracle_mod, kind, k):
     first exceptional call must give the serial chain bit for bit."""
     N, loops = 999, 1000
     g = k % (N + 1)
+    s_k = rc.retry_state(g) if kind == "retry" else rc.case_p_state(g)
     if kind == "retry":
-        s_k = ((12345 - _B) * pow(_A, -1, 1 << 48) - g) & _M48  # t1 = 12345 -> t1 >> 16 == 0
+        assert rc.lcg_pair(s_k, g)[0] >> 16 == 0                  # t1 >> 16 == 0
     else:
-        s_k = next(s for s in range(1, 1 << 31)
-                   if ((((s + g) * _A + _B) & _M48) + g) * _A + _B & _M48 < 2 ** 31)
-    seed = _seed_reaching(s_k, k, N)
+        assert s_k < 2 ** 31 and rc.lcg_pair(s_k, g)[1] < 2 ** 31
+    seed = rc.seed_reaching(s_k, k, N)
     rxi, rw1, rw2, rseeds = oracle_mod.ref_noise_stream(seed, N, loops)
-    assert int(rseeds[k - 1]) & _M48 == s_k  # the construction reached the state
+    assert int(rseeds[k - 1]) & rc.M48 == s_k  # the construction reached the state
     for generator in (1, 0):
         xi, w1, w2, seeds = _gpu_lcg(sqlib, seed, N, loops, generator)
         assert np.array_equal(w1, rw1) and np.array_equal(w2, rw2) and np.array_equal(seeds, rseeds)
         assert np.array_equal(xi, rxi)
+
+
+_LAUNCHES = golden("reference_launches.json")
+
+
+@pytest.mark.parametrize("idx", range(len(_LAUNCHES)))
+def test_recorded_reference_launch_bitwise(gpu, idx):
+    """One run_frame with the device's own draws from the recorded start state
+    against the reference's record: the verdict, lrgEl, lrgVl and the LCG seed;
+    after a stable launch f, x, xx0, omega and runs; after a broken one the
+    uploaded state, unchanged.  (NaNs compare equal whatever their payload.)"""
+    from stochquant_amd import Qm1dChain
+    case, want = rc.decode_launch(_LAUNCHES[idx])
+    with Qm1dChain(case["N"], case["dt"], case["dtau"], pot=case["pot"], C=case["C"], loops=case["loops"],
+                   ordering="serial", lcg_seed=case["seed"], adapt_dtau=False) as g:
+        g.upload(case["f"], case["x"], case["xx0"], omega=case["omega"], runs=case["runs"])
+        g.set_scan(case["lrgEl"], case["lrgVl"], 0)
+        stable = g.run_frame()
+        got, scan, seed, dtau = g.download(), g.scan, g.lcg_seed, g.dtau
+    assert int(bool(stable)) == want["stable"]
+    assert scan["lrgEl"] == want["lrgEl"]
+    assert rc.same(scan["lrgVl"], want["lrgVl"]), (scan["lrgVl"], want["lrgVl"])
+    assert seed == want["seed"]
+    assert dtau == case["dtau"]
+    if want["stable"] == 1:
+        state = dict(f=want["nf"], x=want["nx"], xx0=want["nxx0"], omega=want["omega"],
+                     runs=case["runs"] + case["loops"])
+    else:
+        state = dict(f=case["f"], x=case["x"], xx0=case["xx0"], omega=case["omega"], runs=case["runs"])
+    assert got["runs"] == state["runs"]
+    for k in ("omega", "f", "x", "xx0"):
+        assert rc.same(got[k], state[k]), (k, got[k], state[k])

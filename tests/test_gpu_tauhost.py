@@ -9,6 +9,11 @@ bit: formats, initial state (same unseeded glibc rand() draws,
 tauhost.c:84-102), first printed frame (xavg = 0 -> all -inf), trajectory, Δτ
 controller sequence, omega and trailer lines.  SQ_ORDER=jacobi (and N > 4096) runs the
 Jacobi / Philox frame, checked statistically against its own exact law.
+
+Every run of tests/golden/reference_cli.json, recorded from the reference's
+own host program and kernel (tests/golden/make_reference_sweep.py), is
+reproduced in the default order: exit status, stdout and end file, resumes
+and error paths included.
 """
 import re
 import shutil
@@ -16,6 +21,7 @@ import shutil
 import numpy as np
 import pytest
 
+import reference_cases as rc
 from conftest import golden
 
 pytestmark = pytest.mark.gpu
@@ -159,6 +165,28 @@ def test_reference_runs_byte_identical_to_oracle(gpu, oracle_mod, tmp_path, case
     assert r.returncode == 0
     assert out == r.stdout.decode()
     assert end == (ref_dir / "end").read_text()
+
+
+_CLI = golden("reference_cli.json")
+
+
+@pytest.fixture(scope="module")
+def recorded_runs(gpu, tmp_path_factory):
+    """tauhost.o over the recorded argument lists, in order: a resume starts
+    from the end file tauhost.o itself wrote in the run it continues."""
+    from stochquant_amd import TAUHOST_PATH, run_tauhost
+    run = lambda argv, cwd: run_tauhost([TAUHOST_PATH] + list(argv), cwd=cwd, timeout=120)
+    return rc.replay_cli(run, _CLI, tmp_path_factory.mktemp("recorded"))
+
+
+@pytest.mark.parametrize("idx", range(len(_CLI)), ids=[e["name"] for e in _CLI])
+def test_recorded_reference_run_byte_identical(recorded_runs, idx):
+    """N = 2 ... 200, potID 0 and 3, C 0 and 1, stable, mixed and all-unstable
+    dtau / dt^2, resumes of resumes, an ignored extra argument, a missing
+    start file and a missing argument (where the reference dies of a signal,
+    any failure status with no output stands for it)."""
+    e = _CLI[idx]
+    assert rc.cli_mismatch(e, recorded_runs[e["name"]]) == []
 
 
 def test_serial_order_all_unstable_preset(gpu, tmp_path):
