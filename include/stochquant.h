@@ -855,6 +855,92 @@ int sq_phi4_ens_walkers(sq_phi4_ens *e, int first, int count, int *out /*[count]
 int sq_phi4_ens_exchange_reset(sq_phi4_ens *e, int first, int count, int walkers);
 int sq_phi4_ens_exchange_shape_info(const int dims[3], int out[4]);
 
+/* Swendsen-Wang cluster sweeps of the phi^4 ensemble: the embedded-Ising
+ * update of Brower and Tamayo, the non-local move beside the local samplers
+ * (DESIGN.md §4.3).  Write phi = s |phi|, freeze |phi| and run one
+ * Swendsen-Wang sweep on the signs s, whose couplings are
+ * J_xy = beta |phi_x| |phi_y|; S2 and S4 are even in phi, so the sweep is exact
+ * for exp(-beta S).  Bonds, clusters and flips are decided on the device, one
+ * work-group per lattice.  ABI 6: symbols added, none changed.
+ *
+ * Sweeps.  The handle keeps a 64-bit cluster-sweep counter c, 0 at creation
+ * (sq_phi4_ens_cluster_sweep, sq_phi4_ens_set_cluster_sweep).
+ *
+ * One sweep of replica r holding phi, with record (h = dtau, sig, key) as in
+ * the MALA definition above.  Everything in double from the float field and
+ * the float record, no contraction:
+ *   1. beta = 2 h / (sig sig): the exchange's beta_r, so the sweep is exact for
+ *      the density exp(-beta S) = exp(-S / C^2) that sq_phi4_ens_step_mala and
+ *      sq_phi4_ens_step_hmc sample.
+ *   2. Site index i = (z Ly + y) Lx + x, the row order of the field array.
+ *      o_i is the Philox4x32-10 block at counter {i, 5 << 24, c lo, c hi} under
+ *      the replica's key (stream 5).
+ *   3. Every site owns its three forward bonds, mu = x, y, z, to the periodic
+ *      neighbour j = i + mu^.  With an extent of 2 the forward and the backward
+ *      neighbour are the same site: the two bonds are then separate bonds with
+ *      separate uniforms, as NN counts that product twice.
+ *      t = phi_i phi_j, u_mu = (word mu of o_i + 0.5) 2^-32; the bond is on iff
+ *      t > 0 and u_mu >= exp(-(2 beta) t) (the device's double exp).  A NaN t,
+ *      t = 0 and t < 0 give off.
+ *   4. Clusters are the connected components of the on-bonds; a cluster's
+ *      label is the smallest site index in it.
+ *   5. The cluster with label l flips iff word 3 of o_l is odd.  A flipped
+ *      site has its sign bit toggled; every other bit stays, NaN payloads
+ *      included.  No other field word is written.
+ *   6. c advances by one per sweep.
+ * Parameters, keys, step counters, guard flags, frame state, walkers, all
+ * MALA / HMC / exchange statistics and every accumulator are left alone.
+ *
+ * State per slot, in device memory: cstat[r] = {sweeps, clusters, flipped
+ * clusters, flipped sites, unconverged sweeps}, zero at creation
+ * (sq_phi4_ens_cluster_stats; sq_phi4_ens_cluster_reset clears a range).  The
+ * labelling runs passes of minimum propagation with a bound of sites + 1
+ * passes; a lattice that reached the bound would be left unwritten and
+ * counted as one unconverged sweep.  The bound is what the plain propagation
+ * needs in the worst case, so the count stays 0.
+ *
+ * Limits.  A replica with sig == 0 makes the calls fail with SQ_E_STATE before
+ * anything is launched.  The sweep is exact only as one of the moves of an
+ * exact chain: alternate it with sq_phi4_ens_step_mala or sq_phi4_ens_step_hmc
+ * on thermalised fields.  Alone it is not ergodic, because |phi| is frozen.
+ *
+ * sq_phi4_ens_cluster: nsweeps consecutive sweeps of every replica, enqueued
+ * back to back, one synchronisation at the end.  bonds, nullable:
+ * [nsweeps][nrep][sites] bytes, bits 0 .. 2 = the site's forward bonds x, y, z;
+ * labels, nullable: [nsweeps][nrep][sites]; both are device buffers, read back
+ * once.
+ *
+ * sq_phi4_ens_step_hmc_cluster: per round the sq_phi4_ens_step_hmc launch of
+ * ntraj trajectories, then one sweep; all 2 nrounds launches on the handle's
+ * stream, one synchronisation at the end.  every > 0 needs ntraj % every == 0
+ * (SQ_E_ARG); a measurement sees the field after the trajectory and before the
+ * round's sweep.  series, rec_hmc: as sq_phi4_ens_step_hmc_exchange; bonds,
+ * labels: [nrounds][nrep][sites].  The call is bit for bit the loop
+ * { sq_phi4_ens_step_hmc(ntraj, ..); sq_phi4_ens_cluster(1, ..) } in fields,
+ * series, records, accumulators, counters, flags and statistics.  nleap = 1
+ * serves MALA.  A sweep after each few trajectories together with an exchange
+ * round is the loop of the existing calls.  sq_phi4_ens_perf counts one step
+ * per trajectory and every launch.
+ *
+ * sq_phi4_ens_cluster_shape_info: out = {K, T, LDS bytes, LDS limit} of the
+ * sweep's launch (one work-group per replica, the moments launch's shape);
+ * needs no device; SQ_E_ARG for the shapes sq_phi4_ens_create refuses.
+ * All argument and state checks come before any device work; nsweeps = 0 and
+ * nrounds = 0 do nothing after them. */
+int sq_phi4_ens_cluster(sq_phi4_ens *e, int nsweeps,
+                        unsigned char *bonds /*[nsweeps][R][sites], bits 0..2 = x, y, z forward; nullable*/,
+                        int *labels /*[nsweeps][R][sites]; nullable*/);
+int sq_phi4_ens_cluster_sweep(sq_phi4_ens *e, unsigned long long *c);
+int sq_phi4_ens_set_cluster_sweep(sq_phi4_ens *e, unsigned long long c);
+int sq_phi4_ens_cluster_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][5]*/);
+int sq_phi4_ens_cluster_reset(sq_phi4_ens *e, int first, int count);
+int sq_phi4_ens_cluster_shape_info(const int dims[3], int out[4] /*K, T, LDS bytes, LDS limit*/);
+int sq_phi4_ens_step_hmc_cluster(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                 double *series /*[nrounds ntraj/every][R][4]*/, int measure /*bit 0: correlate*/,
+                                 double *rec_hmc /*[nrounds ntraj][R][4], nullable*/,
+                                 unsigned char *bonds /*[nrounds][R][sites], nullable*/,
+                                 int *labels /*[nrounds][R][sites], nullable*/);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

@@ -240,6 +240,15 @@ SIGNATURES = {
     "sq_phi4_ens_walkers": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "sq_phi4_ens_exchange_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "sq_phi4_ens_exchange_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_cluster": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_cluster_sweep": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "sq_phi4_ens_set_cluster_sweep": (ctypes.c_int, [_P, ctypes.c_ulonglong]),
+    "sq_phi4_ens_cluster_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ens_cluster_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_ens_cluster_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_step_hmc_cluster": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    _D, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_ubyte),
+                                                    ctypes.POINTER(ctypes.c_int)]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4

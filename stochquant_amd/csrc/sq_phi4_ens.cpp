@@ -77,6 +77,13 @@ struct sq_phi4_ens {
     int *walker = nullptr;               // [R] the label of the field each slot holds; r at creation
     double *xrec = nullptr;              // the last exchange call's records: pinned host memory the kernel writes
     size_t xrec_cap = 0;                 // ... in doubles
+    unsigned long long csweep = 0;       // the cluster-sweep counter
+    long long *cstat = nullptr;          // [R][5] sweeps, clusters, flipped clusters, flipped sites, unconverged
+                                         // sweeps; zero at creation, cleared by sq_phi4_ens_cluster_reset only
+    unsigned char *cbonds = nullptr;     // the last cluster call's bond records: device memory, read back once
+    size_t cbonds_cap = 0;               // ... in bytes
+    int *clabels = nullptr;              // ... and its label records
+    size_t clabels_cap = 0;              // ... in ints
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };
@@ -193,6 +200,13 @@ void release_phi4_ens(sq_phi4_ens *e) {
     e->walker = nullptr;
     e->xrec = nullptr;
     e->xrec_cap = 0;
+    (void)hipFree(e->cstat);
+    (void)hipFree(e->cbonds);
+    (void)hipFree(e->clabels);
+    e->cstat = nullptr;
+    e->cbonds = nullptr;
+    e->clabels = nullptr;
+    e->cbonds_cap = e->clabels_cap = 0;
     e->frec = nullptr;
     e->fG = e->fS1 = e->ftmp = nullptr;
     e->fN = nullptr;
@@ -331,6 +345,8 @@ int sq_phi4_ens_create(const sq_params *p, int nrep, const unsigned long long *s
         SQ_HIP(hipMemset(e->pN, 0, sizeof(long long) * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->xstat, sizeof(long long) * 2 * (size_t)nrep));
         SQ_HIP(hipMemset(e->xstat, 0, sizeof(long long) * 2 * (size_t)nrep));
+        SQ_HIP(hipMalloc(&e->cstat, sizeof(long long) * 5 * (size_t)nrep));
+        SQ_HIP(hipMemset(e->cstat, 0, sizeof(long long) * 5 * (size_t)nrep));
         SQ_HIP(hipMalloc(&e->walker, sizeof(int) * (size_t)nrep));
         {
             std::vector<int> id((size_t)nrep);
@@ -1679,6 +1695,198 @@ int sq_phi4_ens_exchange_reset(sq_phi4_ens *e, int first, int count, int walkers
 }
 
 int sq_phi4_ens_exchange_shape_info(const int dims[3], int out[4]) {
+    if (!dims || !out) return fail(SQ_E_ARG, "null argument");
+    if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
+    const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
+    out[0] = s.K;
+    out[1] = s.T;
+    out[2] = s.mom_lds_bytes;
+    out[3] = sq::kPhi4EnsLdsBytes;
+    return SQ_OK;
+}
+
+}  // extern "C"
+
+// ---- Swendsen-Wang cluster sweeps (sq_phi4_ens_cluster.hip) ----
+namespace {
+
+// What stands against a cluster sweep, checked before any device work.
+int ens_cluster_state(const sq_phi4_ens *e) {
+    for (int r = 0; r < e->R; ++r)
+        if (ens_rec(e->rep[(size_t)r]).sig == 0.0f)
+            return fail(SQ_E_STATE, "a cluster sweep needs C != 0 in every replica (sig = sqrt(2 dtau) C is zero in "
+                                    "fp32): beta = 2 dtau / sig^2 has no value");
+    return SQ_OK;
+}
+
+// The device buffers of a call's records: nsweeps sweeps of [R][sites] each, either nullable.
+int ens_cluster_bufs(sq_phi4_ens *e, size_t nb, size_t nl) {
+    if (nb > e->cbonds_cap) {
+        (void)hipFree(e->cbonds);
+        e->cbonds = nullptr;
+        e->cbonds_cap = 0;
+        SQ_HIP(hipMalloc(&e->cbonds, nb));
+        e->cbonds_cap = nb;
+    }
+    if (nl > e->clabels_cap) {
+        (void)hipFree(e->clabels);
+        e->clabels = nullptr;
+        e->clabels_cap = 0;
+        SQ_HIP(hipMalloc(&e->clabels, sizeof(int) * nl));
+        e->clabels_cap = nl;
+    }
+    return SQ_OK;
+}
+
+// Enqueue sweep e->csweep + i; bonds, labels: the call's device buffers, nullable.
+int ens_cluster_enqueue(sq_phi4_ens *e, int i, bool bonds, bool labels) {
+    const size_t per = (size_t)e->R * e->sites;
+    sq::Phi4EnsClusterArgs w{};
+    w.stat = e->cstat;
+    w.bonds = bonds ? e->cbonds + per * (size_t)i : nullptr;
+    w.labels = labels ? e->clabels + per * (size_t)i : nullptr;
+    w.c = e->csweep + (unsigned long long)i;
+    const hipError_t he = sq::phi4_ens_cluster_launch(ens_args(e), w, e->R, e->stream);
+    if (he != hipSuccess) return fail(SQ_E_HIP, std::string("phi4_ens_cluster_launch: ") + hipGetErrorString(he));
+    e->launches++;
+    return SQ_OK;
+}
+
+// The records of nsweeps sweeps back to the caller, behind the synchronisation.
+int ens_cluster_readback(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels) {
+    const size_t n = (size_t)nsweeps * (size_t)e->R * e->sites;
+    if (bonds) SQ_HIP(hipMemcpy(bonds, e->cbonds, n, hipMemcpyDeviceToHost));
+    if (labels) SQ_HIP(hipMemcpy(labels, e->clabels, sizeof(int) * n, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sq_phi4_ens_cluster_sweep(sq_phi4_ens *e, unsigned long long *c) {
+    if (!e || !c) return fail(SQ_E_ARG, "null argument");
+    *c = e->csweep;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_set_cluster_sweep(sq_phi4_ens *e, unsigned long long c) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    e->csweep = c;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_cluster(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsweeps < 0) return fail(SQ_E_ARG, "nsweeps must be >= 0");
+    int rc = ens_cluster_state(e);
+    if (rc) return rc;
+    if (nsweeps == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    rc = ens_sync_recs(e);
+    if (rc) return rc;
+    const size_t n = (size_t)nsweeps * (size_t)e->R * e->sites;
+    rc = ens_cluster_bufs(e, bonds ? n : 0, labels ? n : 0);
+    if (rc) return rc;
+    for (int i = 0; i < nsweeps && !rc; ++i) rc = ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr);
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (rc) return rc;
+    SQ_HIP(he);
+    rc = ens_cluster_readback(e, nsweeps, bonds, labels);
+    if (rc) return rc;
+    e->csweep += (unsigned long long)nsweeps;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_step_hmc_cluster(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                 double *series, int measure, double *rec_hmc, unsigned char *bonds, int *labels) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nrounds < 0) return fail(SQ_E_ARG, "nrounds must be >= 0");
+    if (ntraj < 0) return fail(SQ_E_ARG, "ntraj must be >= 0");
+    if (nleap < 1 || nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap must lie in [1, 4096]");
+    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a trajectory measures no momenta");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
+    if (every > 0 && ntraj % every != 0)
+        return fail(SQ_E_ARG, "every must divide ntraj: the measurements are those of the separate calls");
+    int rc = ens_cluster_state(e);  // the trajectories' C != 0 as well
+    if (rc) return rc;
+    if (nrounds == 0) return SQ_OK;
+    const bool corr = (measure & 1) != 0;
+    DeviceGuard g(e->dev);
+    rc = ens_sync_recs(e);
+    if (rc) return rc;
+    rc = ens_hmc_stat(e);
+    if (rc) return rc;
+    const size_t per = (every > 0 && series) ? (size_t)(ntraj / every) * (size_t)e->R * 4 : 0;  // a round's series
+    const size_t nd = per * (size_t)nrounds;
+    const size_t perh = rec_hmc ? (size_t)ntraj * (size_t)e->R * 4 : 0;
+    const size_t nm = perh * (size_t)nrounds;
+    const size_t n = (size_t)nrounds * (size_t)e->R * e->sites;
+    rc = ens_pinned(e->series, e->series_cap, nd);
+    if (rc) return rc;
+    rc = ens_pinned(e->hrec, e->hrec_cap, nm);
+    if (rc) return rc;
+    rc = ens_cluster_bufs(e, bonds ? n : 0, labels ? n : 0);
+    if (rc) return rc;
+    sq::Phi4EnsHmcArgs w{};
+    w.stat = e->hstat;
+    w.nleap = nleap;
+    w.randomize = randomize != 0 ? 1 : 0;
+    const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
+    for (int i = 0; i < nrounds && !rc; ++i) {
+        if (ntraj > 0) {
+            sq::Phi4EnsArgs a = ens_args(e);
+            a.adv = e->adv + (unsigned long long)i * (unsigned long long)ntraj;
+            a.nsteps = ntraj;
+            a.every = (nd || corr) ? every : 0;
+            a.series = nd ? e->series + per * (size_t)i : nullptr;
+            w.rec = nm ? e->hrec + perh * (size_t)i : nullptr;
+            const hipError_t he = sq::phi4_ens_hmc_launch(a, w, corr ? &c : nullptr, e->R, e->stream);
+            if (he != hipSuccess) {
+                rc = fail(SQ_E_HIP, std::string("phi4_ens_hmc_launch: ") + hipGetErrorString(he));
+                break;
+            }
+            e->launches++;
+        }
+        rc = ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr);
+    }
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (rc) return rc;
+    SQ_HIP(he);
+    if (nd) memcpy(series, e->series, sizeof(double) * nd);
+    if (nm) memcpy(rec_hmc, e->hrec, sizeof(double) * nm);
+    rc = ens_cluster_readback(e, nrounds, bonds, labels);
+    if (rc) return rc;
+    const unsigned long long tot = (unsigned long long)nrounds * (unsigned long long)ntraj;
+    e->adv += tot;  // one count per trajectory
+    for (auto &r : e->rep) r.step += tot;
+    e->steps_total += (long long)tot * e->R;
+    e->csweep += (unsigned long long)nrounds;
+    return SQ_OK;
+}
+
+int sq_phi4_ens_cluster_stats(sq_phi4_ens *e, int first, int count, long long *out) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (!out) return fail(SQ_E_ARG, "null argument");
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemcpy(out, e->cstat + 5 * (size_t)first, sizeof(long long) * 5 * (size_t)count, hipMemcpyDeviceToHost));
+    return SQ_OK;
+}
+
+int sq_phi4_ens_cluster_reset(sq_phi4_ens *e, int first, int count) {
+    int rc = ens_range(e, first, count);
+    if (rc) return rc;
+    if (count == 0) return SQ_OK;
+    DeviceGuard g(e->dev);
+    SQ_HIP(hipMemset(e->cstat + 5 * (size_t)first, 0, sizeof(long long) * 5 * (size_t)count));
+    SQ_HIP(hipDeviceSynchronize());
+    return SQ_OK;
+}
+
+int sq_phi4_ens_cluster_shape_info(const int dims[3], int out[4]) {
     if (!dims || !out) return fail(SQ_E_ARG, "null argument");
     if (const char *why = ens_dims_error(dims[0], dims[1], dims[2])) return fail(SQ_E_ARG, why);
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);

@@ -303,4 +303,24 @@ inline int phi4_ens_xchg_pairs(int nlad, unsigned long long x) { return (nlad - 
 // launches nothing and is hipSuccess.  a.flags, a.series, a.nsteps, a.every, a.adv are not used.
 hipError_t phi4_ens_exchange_launch(const Phi4EnsArgs &a, const Phi4EnsXchgArgs &w, int nrep, hipStream_t s);
 
+// ---- Swendsen-Wang cluster sweeps (sq_phi4_ens_cluster.hip) ----
+// The Philox stream of a sweep's per-site blocks: counter {site, kPhi4EnsStreamCluster << 24, c lo, c hi} under the
+// replica's key, words 0 .. 2 the uniforms of the site's forward bonds x, y, z, word 3 the flip bit of the cluster
+// the site is the root of.  The sixth stream.
+constexpr uint32_t kPhi4EnsStreamCluster = 5;
+
+// One sweep: its counter, the replicas' counters and the optional records of this sweep.
+struct Phi4EnsClusterArgs {
+    long long *stat;         // [R][5] = sweeps, clusters, flipped clusters, flipped sites, unconverged sweeps
+                             // (device memory)
+    unsigned char *bonds;    // [R][sites] bits 0 .. 2 = the site's forward bonds x, y, z (device memory); nullable
+    int *labels;             // [R][sites] the smallest site index of the site's cluster (device memory); nullable
+    unsigned long long c;    // the sweep counter
+};
+// Sweep w.c of every replica in one launch (phi4_ens_cluster_kernel): one work-group per replica, the moments
+// launch's work-group shape and LDS layout.  Only sign bits of a.field change.  Every replica's sig must be
+// non-zero (the caller checks: the kernel divides by sig^2).  a.flags, a.series, a.nsteps, a.every, a.adv are not
+// used.
+hipError_t phi4_ens_cluster_launch(const Phi4EnsArgs &a, const Phi4EnsClusterArgs &w, int nrep, hipStream_t s);
+
 }  // namespace sq

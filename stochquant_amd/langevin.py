@@ -992,6 +992,103 @@ class Phi4Ensemble:
         _lib.call("sq_phi4_ens_exchange_shape_info", dims, out)
         return dict(zip(("K", "T", "lds_bytes", "lds_limit"), (int(v) for v in out)))
 
+    @property
+    def cluster_sweep(self):
+        c = ctypes.c_ulonglong(0)
+        _lib.call("sq_phi4_ens_cluster_sweep", self._h, ctypes.byref(c))
+        return c.value
+
+    @cluster_sweep.setter
+    def cluster_sweep(self, v):
+        _lib.call("sq_phi4_ens_set_cluster_sweep", self._h, ctypes.c_ulonglong(int(v)))
+
+    def _cluster_records(self, n, record):
+        sites = self.shape[0] * self.shape[1] * self.shape[2]
+        if not record:
+            return None, None
+        return np.zeros((n, self.R, sites), dtype=np.uint8), np.zeros((n, self.R, sites), dtype=np.int32)
+
+    def cluster(self, sweeps=1, record=False):
+        """`sweeps` Swendsen-Wang cluster sweeps of every replica on the device,
+        back to back (sq_phi4_ens_cluster; include/stochquant.h has the
+        definition).  The embedded-Ising update of Brower and Tamayo: φ = s|φ|
+        with |φ| frozen, every forward bond between sites of one sign switched
+        on with probability 1 - exp(-2β φ_i φ_j), β = 1 / C², the clusters of
+        the on-bonds labelled by their smallest site index, and every cluster's
+        sign flipped with probability ½ -- all from the replica's Philox key at
+        the counter `cluster_sweep`, which advances by one per sweep.  Only
+        sign bits of the fields change; parameters, counters, flags, walkers
+        and every accumulator stay.  record=True: returns (bonds, labels), the
+        (sweeps, R, sites) uint8 array of the sites' forward bonds (bits 0, 1,
+        2 = x, y, z) and the (sweeps, R, sites) int32 array of their cluster
+        labels; else None.
+
+        The sweep is exact for exp(-S / C²), the density `step_mala` and
+        `step_hmc` sample, but alone it is not ergodic (|φ| never moves):
+        alternate it with trajectories on thermalised fields
+        (`step_hmc_cluster`).  Every replica needs C != 0 (StochQuantError
+        otherwise)."""
+        sweeps = int(sweeps)
+        bonds, labels = self._cluster_records(max(sweeps, 0), record)
+        _lib.call("sq_phi4_ens_cluster", self._h, sweeps,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
+        return (bonds, labels) if record else None
+
+    def step_hmc_cluster(self, rounds, ntraj=1, nleap=1, randomize=False, every=0, correlate=False, record=False):
+        """`rounds` times: `step_hmc(ntraj, nleap, randomize, every, correlate)`,
+        then one `cluster` sweep -- all launches enqueued back to back with one
+        synchronisation at the end (sq_phi4_ens_step_hmc_cluster).  Bit for bit
+        the loop of the separate calls in everything.  every = k > 0 needs
+        ntraj % k == 0 and returns the (rounds * ntraj // k, R, 4) sums, taken
+        of the field a replica holds after its trajectory and before the
+        round's sweep; else None.  record=True: returns (series, rec_hmc,
+        bonds, labels), the (rounds * ntraj, R, 4) trajectory records of
+        `step_hmc` and the (rounds, R, sites) records of `cluster`.  nleap=1 is
+        MALA with cluster sweeps."""
+        rounds, ntraj, nleap, every = int(rounds), int(ntraj), int(nleap), int(every)
+        if nleap < 1 or nleap > 4096:
+            raise ValueError("step_hmc_cluster: nleap must lie in [1, 4096]")
+        if correlate and every < 1:
+            raise ValueError("step_hmc_cluster: correlate=True needs every >= 1")
+        if every > 0 and ntraj % every != 0:
+            raise ValueError("step_hmc_cluster: every must divide ntraj")
+        nr, nj = max(rounds, 0), max(ntraj, 0)
+        ser = np.zeros((nr * (nj // every), self.R, 4)) if every > 0 else None
+        rh = np.zeros((nr * nj, self.R, 4)) if record else None
+        bonds, labels = self._cluster_records(nr, record)
+        _lib.call("sq_phi4_ens_step_hmc_cluster", self._h, rounds, ntraj, nleap, 1 if randomize else 0, every,
+                  _dptr(ser) if ser is not None and ser.size else None, 1 if correlate else 0,
+                  _dptr(rh) if rh is not None and rh.size else None,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
+        return (ser, rh, bonds, labels) if record else ser
+
+    def cluster_stats(self, first=0, count=None):
+        """(count, 5) int64: sweeps, clusters, flipped clusters, flipped sites
+        and unconverged sweeps (always 0: the labelling's pass bound is its
+        worst case) per replica, since creation or `cluster_reset`
+        (sq_phi4_ens_cluster_stats)."""
+        k = self._count(first, count)
+        out = np.zeros((max(k, 0), 5), dtype=np.int64)
+        _lib.call("sq_phi4_ens_cluster_stats", self._h, int(first), k,
+                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def cluster_reset(self, first=0, count=None):
+        """Clear the cluster counters of replicas first .. first + count."""
+        _lib.call("sq_phi4_ens_cluster_reset", self._h, int(first), self._count(first, count))
+
+    @staticmethod
+    def cluster_shape_info(shape):
+        """What the cluster sweep's launch asks for, without a device: K quads
+        per lane, T lanes, dynamic LDS bytes and the LDS limit -- the moments
+        launch's shape, one work-group per replica."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 4)()
+        _lib.call("sq_phi4_ens_cluster_shape_info", dims, out)
+        return dict(zip(("K", "T", "lds_bytes", "lds_limit"), (int(v) for v in out)))
+
     def step_flow(self, n=1, every=1, correlate=False, scheme="euler"):
         """n steps of every replica in one launch, as `step`, with a flow
         measurement after each every-th step (every >= 1, `set_flow` first;
