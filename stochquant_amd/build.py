@@ -32,8 +32,9 @@ DEVICE_SOURCES = ["sq_phi4.hip", "sq_phi4_run.hip", "sq_qm1d.hip", "sq_qm1d_ens.
                   "sq_phi4_ens_flow.hip", "sq_phi4_ens_flow_frames.hip", "sq_phi4_ens_mala.hip", "sq_phi4_ens_hmc.hip", "sq_phi4_ens_exchange.hip", "sq_phi4_ens_cluster.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
 HOST_SOURCES = ["sq_core.cpp", "sq_comm.cpp", "sq_phi4_create.cpp", "sq_phi4_plan.cpp", "sq_phi4_steps.cpp",
                 "sq_phi4_frames.cpp", "sq_phi4_fields.cpp", "sq_qm1d_host.cpp", "sq_ens.cpp", "sq_phi4_ens.cpp",
+                "sq_phi4_ens_frames.cpp", "sq_phi4_ens_corr.cpp", "sq_phi4_ens_flow.cpp", "sq_phi4_ens_samplers.cpp",
                 "sq_diag.cpp", "sq_io.cpp"]
-HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h", "sq_phi4_ens_flow_dev.h", "sq_phi4_ens_mala_dev.h",
+HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_buf.h", "sq_phi4_ens_host.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h", "sq_phi4_ens_flow_dev.h", "sq_phi4_ens_mala_dev.h",
            "sq_qm1d_math.h"]
 # device sources that include another one
 INCLUDES = {"sq_phi4_run.hip": ["sq_phi4.hip"], "sq_phi4_ens.hip": ["sq_phi4.hip"],
