@@ -941,6 +941,74 @@ int sq_phi4_ens_step_hmc_cluster(sq_phi4_ens *e, int nrounds, int ntraj, int nle
                                  unsigned char *bonds /*[nrounds][R][sites], nullable*/,
                                  int *labels /*[nrounds][R][sites], nullable*/);
 
+/* Cluster sums of a sweep: the improved estimators.  With
+ * M = sum_C s_C M_C, M_C = sum_{i in C} |phi_i| and independent cluster signs
+ * s_C = +-1, the average over the signs is known in closed form:
+ *   <(sum phi)^2> = <sum_C M_C^2>,
+ *   <(sum phi)^4> = <3 (sum_C M_C^2)^2 - 2 sum_C M_C^4>,
+ *   <|sum_i phi_i e^{i p x_i}|^2> = <sum_C |sum_{i in C} |phi_i| e^{i p x_i}|^2>,
+ * the susceptibility, the Binder cumulant and the second-moment correlation
+ * length, with a variance well below the naive sums'.  The sweep's kernel
+ * forms the sums while the labels are on chip.  ABI 6: symbols added, none
+ * changed.  The three calls are named sq_phi4_ensemble_*: the family
+ * sq_phi4_ens_* is a closed table of 72 entry points
+ * (tests/test_phi4_ens_null_boundary.py counts them).
+ *
+ * One sweep with the sums, of replica r holding phi.  All arithmetic in double
+ * from the float field, no contraction:
+ *   1. Steps 1 - 6 of the sweep above, unchanged: fields, the sweep counter,
+ *      cstat and every other state are bit for bit those of the plain call.
+ *   2. Per-site weights, fixed-point integers, so that a cluster's sums are
+ *      exact whatever the order of the lanes.  a = |phi_i| in double (of the
+ *      field the sweep started from; a flip changes no magnitude).  A site is
+ *      saturated when a is NaN, infinite or >= 2^15: q = 0 and all
+ *      a_mu = b_mu = 0, and it is counted.  Otherwise q_i = floor(a 2^32) as
+ *      int64 and, per axis mu = x, y, z with (c, s) =
+ *      sq_phi4_ens_momentum_table(L_mu, 1) and k the site's coordinate on that
+ *      axis, a_mu,i = rint((a c[k]) 2^32), ties to even, and b_mu,i the same
+ *      with s[k]: the product is rounded once in double, the scaling by 2^32
+ *      is exact.  Saturated sites take part in bonds and labels as ever.
+ *   3. Per cluster C with label l, as int64: M_C = sum q_i, A_mu,C = sum a_mu,i,
+ *      B_mu,C = sum b_mu,i.  At most 32,768 sites: |sum| < 2^62.
+ *   4. Per replica and sweep a record of 8 doubles.  With m_C = (double)M_C
+ *      2^-32, alpha, beta likewise of A, B:
+ *        I2 = sum_C m_C^2, I4 = sum_C (m_C^2)^2,
+ *        F_mu = sum_C alpha_mu,C^2 + sum_C beta_mu,C^2 for mu = x, y, z,
+ *        Mmax = max_C m_C, Mtot = (double)(sum_C M_C) 2^-32,
+ *        nsat = the number of saturated sites.
+ *      An unconverged sweep writes eight zeros except nsat = -1 (and no sums).
+ *      Every sum over clusters runs over the roots in the kernel's fixed order
+ *      (lane, then the kernel's fold), the same bits from run to run; against
+ *      another order it is within n_clusters 2^-52 relative.  Mmax, Mtot and
+ *      nsat are exact.
+ *
+ * sq_phi4_ensemble_cluster_improved: sq_phi4_ens_cluster with series
+ * [nsweeps][nrep][8] = I2, I4, F_x, F_y, F_z, Mmax, Mtot, nsat (required) and
+ * weights, nullable: [nsweeps][nrep][sites][7] = M, A_x, B_x, A_y, B_y, A_z,
+ * B_z at the root's index, 0 elsewhere.
+ * sq_phi4_ensemble_step_hmc_cluster_improved: sq_phi4_ens_step_hmc_cluster with
+ * cseries [nrounds][nrep][8] (required) and weights [nrounds][nrep][sites][7].
+ * Checks and errors are the plain calls': a replica with sig == 0 is
+ * SQ_E_STATE, and nothing is launched on a bad argument.
+ * sq_phi4_ensemble_cluster_improved_shape_info: out = {K, T, LDS bytes, LDS limit,
+ * park} of that launch; park = 1: the labels wait in device memory while the
+ * LDS image serves as the accumulators (K = 8), 0: in registers.  Needs no
+ * device. */
+int sq_phi4_ensemble_cluster_improved(sq_phi4_ens *e, int nsweeps, double *series /*[nsweeps][R][8]*/,
+                                 unsigned char *bonds /*[nsweeps][R][sites], nullable*/,
+                                 int *labels /*[nsweeps][R][sites], nullable*/,
+                                 long long *weights /*[nsweeps][R][sites][7] int64: M, A_x, B_x, A_y, B_y, A_z, B_z at
+                                                      the root's index, 0 elsewhere; nullable*/);
+int sq_phi4_ensemble_step_hmc_cluster_improved(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                          double *series /*[nrounds ntraj/every][R][4]*/,
+                                          int measure /*bit 0: correlate*/,
+                                          double *rec_hmc /*[nrounds ntraj][R][4], nullable*/,
+                                          unsigned char *bonds /*[nrounds][R][sites], nullable*/,
+                                          int *labels /*[nrounds][R][sites], nullable*/,
+                                          double *cseries /*[nrounds][R][8]*/,
+                                          long long *weights /*[nrounds][R][sites][7], nullable*/);
+int sq_phi4_ensemble_cluster_improved_shape_info(const int dims[3], int out[5] /*K, T, LDS bytes, LDS limit, park*/);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

@@ -249,6 +249,13 @@ SIGNATURES = {
     "sq_phi4_ens_step_hmc_cluster": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                     _D, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_ubyte),
                                                     ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ensemble_cluster_improved": (ctypes.c_int, [_P, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_ubyte),
+                                                    ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ensemble_step_hmc_cluster_improved": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.c_int, _D, ctypes.c_int, _D,
+                                                             ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int),
+                                                             _D, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_ensemble_cluster_improved_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4

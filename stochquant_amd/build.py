@@ -29,7 +29,8 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 ARCH = os.environ.get("SQ_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SOURCES = ["sq_phi4.hip", "sq_phi4_run.hip", "sq_qm1d.hip", "sq_qm1d_ens.hip", "sq_qm1d_gs.hip", "sq_phi4_ens.hip",
-                  "sq_phi4_ens_flow.hip", "sq_phi4_ens_flow_frames.hip", "sq_phi4_ens_mala.hip", "sq_phi4_ens_hmc.hip", "sq_phi4_ens_exchange.hip", "sq_phi4_ens_cluster.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
+                  "sq_phi4_ens_flow.hip", "sq_phi4_ens_flow_frames.hip", "sq_phi4_ens_mala.hip", "sq_phi4_ens_hmc.hip", "sq_phi4_ens_exchange.hip", "sq_phi4_ens_cluster.hip",
+                  "sq_phi4_ens_cluster_improved.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
 HOST_SOURCES = ["sq_core.cpp", "sq_comm.cpp", "sq_phi4_create.cpp", "sq_phi4_plan.cpp", "sq_phi4_steps.cpp",
                 "sq_phi4_frames.cpp", "sq_phi4_fields.cpp", "sq_qm1d_host.cpp", "sq_ens.cpp", "sq_phi4_ens.cpp",
                 "sq_phi4_ens_frames.cpp", "sq_phi4_ens_corr.cpp", "sq_phi4_ens_flow.cpp", "sq_phi4_ens_samplers.cpp",
@@ -43,7 +44,8 @@ INCLUDES = {"sq_phi4_run.hip": ["sq_phi4.hip"], "sq_phi4_ens.hip": ["sq_phi4.hip
             "sq_phi4_ens_mala.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
             "sq_phi4_ens_hmc.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
             "sq_phi4_ens_exchange.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_cluster.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"]}
+            "sq_phi4_ens_cluster.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
+            "sq_phi4_ens_cluster_improved.hip": ["sq_phi4_ens_cluster.hip", "sq_phi4_ens.hip", "sq_phi4.hip"]}
 # per-source flags beside COMMON.  sq_phi4_ens_mala.hip: the step loop calls the double exp once per step, and
 # machine LICM hoists the twenty-odd 64-bit constants of its polynomial out of the loop into vector registers,
 # where they stay for the whole call: the K = 8 instances then spill to private memory.  The kernels of that file

@@ -323,4 +323,29 @@ struct Phi4EnsClusterArgs {
 // used.
 hipError_t phi4_ens_cluster_launch(const Phi4EnsArgs &a, const Phi4EnsClusterArgs &w, int nrep, hipStream_t s);
 
+// ---- the sweep with cluster sums (sq_phi4_ens_cluster_improved.hip) ----
+// What the sums of one sweep need beside Phi4EnsClusterArgs: an argument of its own, the plain instances keep
+// their argument list.
+struct Phi4EnsClusterSumArgs {
+    double *series;      // [R][8] = I2, I4, Fx, Fy, Fz, Mmax, Mtot, nsat, device-visible (pinned host memory)
+    long long *weights;  // [R][sites][7] = M, A_x, B_x, A_y, B_y, A_z, B_z at the root's index, 0 elsewhere (device
+                         // memory); nullable
+    const double *tab;   // c | s of the unit momentum of x [2][Lx], then y [2][Ly], then z [2][Lz]
+                         // (sq_phi4_ens_momentum_table's values, device memory)
+    int *park;           // [R][sites] where a lane's labels and its roots' partial sums wait when the shape parks
+                         // them (device memory); else not used
+};
+// Where the labels wait while the image serves as the accumulators: the lane's registers (K <= 4) or device
+// memory (K = 8: no 32 registers to spare).  The work-group shape is the plain sweep's, the LDS 32 bytes more.
+struct Phi4EnsClusterSumShape {
+    int K, T;
+    int lds_bytes;
+    int park;  // 0 registers, 1 device memory
+};
+Phi4EnsClusterSumShape phi4_ens_cluster_sum_shape(int sites);
+// phi4_ens_cluster_launch with the cluster sums of the sweep's labels (the kernel's second kind of instance):
+// fields, statistics and records are the plain launch's bit for bit.
+hipError_t phi4_ens_cluster_improved_launch(const Phi4EnsArgs &a, const Phi4EnsClusterArgs &w,
+                                            const Phi4EnsClusterSumArgs &x, int nrep, hipStream_t s);
+
 }  // namespace sq

@@ -94,6 +94,10 @@ struct sq_phi4_ens {
                                          // sweeps; zero at creation, cleared by sq_phi4_ens_cluster_reset only
     sq::DevBuf<unsigned char> cbonds;    // the last cluster call's bond records: device memory, read back once
     sq::DevBuf<int> clabels;             // ... and its label records
+    sq::PinBuf<double> cser;             // the last improved cluster call's records, written by the kernel
+    sq::DevBuf<long long> cweights;      // ... and its cluster sums: device memory, read back once
+    sq::DevBuf<double> ctab;             // the unit momentum's tables c | s of x, y, z (first improved call on)
+    sq::DevBuf<int> cpark;               // [R][sites] the parked labels of a shape that parks them (likewise)
     hipStream_t stream = nullptr;
     long long steps_total = 0, launches = 0;
 };

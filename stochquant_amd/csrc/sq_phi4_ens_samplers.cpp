@@ -342,34 +342,111 @@ int ens_cluster_state(const sq_phi4_ens *e) {
     return ens_needs_noise(e, "a cluster sweep", "beta = 2 dtau / sig^2 has no value");
 }
 
-// The device buffers of a call's records: nsweeps sweeps of [R][sites] each, where the caller wants them.
-int ens_cluster_bufs(sq_phi4_ens *e, int nsweeps, bool bonds, bool labels) {
+// What a call with the cluster sums returns beside the plain call's records.
+struct EnsSums {
+    double *series;      // [n][R][8]
+    long long *weights;  // [n][R][sites][7], nullable
+};
+
+// The device buffers of a call's records: nsweeps sweeps of [R][sites] each, where the caller wants them; x: the
+// call takes the cluster sums, with their series, the tables and, where the shape parks its labels, the scratch.
+int ens_cluster_bufs(sq_phi4_ens *e, int nsweeps, bool bonds, bool labels, const EnsSums *x) {
     const size_t n = (size_t)nsweeps * (size_t)e->R * e->sites;
     int rc = ens_reserve(e->cbonds, bonds ? n : 0);
     if (!rc) rc = ens_reserve(e->clabels, labels ? n : 0);
-    return rc;
+    if (rc || !x) return rc;
+    rc = ens_reserve(e->cser, 8 * (size_t)nsweeps * (size_t)e->R);
+    if (!rc) rc = ens_reserve(e->cweights, x->weights ? 7 * n : 0);
+    if (!rc && sq::phi4_ens_cluster_sum_shape((int)e->sites).park) rc = ens_reserve(e->cpark, (size_t)e->R * e->sites);
+    if (rc) return rc;
+    // an unconverged sweep leaves its rows of the sums unwritten: zeros
+    if (x->weights) SQ_HIP(hipMemsetAsync(e->cweights.data(), 0, sizeof(long long) * 7 * n, e->stream));
+    if (e->ctab.data()) return SQ_OK;
+    const int L[3] = {e->Lx, e->Ly, e->Lz};
+    std::vector<double> tab(2 * (size_t)(L[0] + L[1] + L[2]));
+    size_t at = 0;
+    for (int mu = 0; mu < 3 && !rc; at += 2 * (size_t)L[mu], ++mu)
+        rc = sq_phi4_ens_momentum_table(L[mu], 1, &tab[at], &tab[at + (size_t)L[mu]]);
+    if (!rc) rc = ens_reserve(e->ctab, tab.size());
+    if (rc) return rc;
+    SQ_HIP(hipMemcpy(e->ctab.data(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    return SQ_OK;
 }
 
-// Enqueue sweep e->csweep + i; bonds, labels: the call records them.
-int ens_cluster_enqueue(sq_phi4_ens *e, int i, bool bonds, bool labels) {
+// Enqueue sweep e->csweep + i; bonds, labels: the call records them; x: with the cluster sums.
+int ens_cluster_enqueue(sq_phi4_ens *e, int i, bool bonds, bool labels, const EnsSums *x) {
     const size_t per = (size_t)e->R * e->sites;
     sq::Phi4EnsClusterArgs w{};
     w.stat = e->cstat.data();
     w.bonds = bonds ? e->cbonds.data() + per * (size_t)i : nullptr;
     w.labels = labels ? e->clabels.data() + per * (size_t)i : nullptr;
     w.c = e->csweep + (unsigned long long)i;
-    const hipError_t he = sq::phi4_ens_cluster_launch(ens_args(e), w, e->R, e->stream);
+    hipError_t he;
+    if (x) {
+        sq::Phi4EnsClusterSumArgs xs{};
+        xs.series = e->cser.data() + 8 * (size_t)i * (size_t)e->R;
+        xs.weights = x->weights ? e->cweights.data() + 7 * per * (size_t)i : nullptr;
+        xs.tab = e->ctab.data();
+        xs.park = e->cpark.data();
+        he = sq::phi4_ens_cluster_improved_launch(ens_args(e), w, xs, e->R, e->stream);
+    } else {
+        he = sq::phi4_ens_cluster_launch(ens_args(e), w, e->R, e->stream);
+    }
     if (he != hipSuccess) return fail(SQ_E_HIP, std::string("phi4_ens_cluster_launch: ") + hipGetErrorString(he));
     e->launches++;
     return SQ_OK;
 }
 
 // Behind the synchronisation: the records of nsweeps sweeps to the caller, and the sweep counter.
-int ens_cluster_end(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels) {
+int ens_cluster_end(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels, const EnsSums *x) {
     const size_t n = (size_t)nsweeps * (size_t)e->R * e->sites;
     if (bonds) SQ_HIP(hipMemcpy(bonds, e->cbonds.data(), n, hipMemcpyDeviceToHost));
     if (labels) SQ_HIP(hipMemcpy(labels, e->clabels.data(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    if (x) {
+        memcpy(x->series, e->cser.data(), sizeof(double) * 8 * (size_t)nsweeps * (size_t)e->R);
+        if (x->weights)
+            SQ_HIP(hipMemcpy(x->weights, e->cweights.data(), sizeof(long long) * 7 * n, hipMemcpyDeviceToHost));
+    }
     e->csweep += (unsigned long long)nsweeps;
+    return SQ_OK;
+}
+
+// sq_phi4_ens_cluster and, x non-null, its _improved form.
+int ens_cluster(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels, const EnsSums *x) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsweeps < 0) return fail(SQ_E_ARG, "nsweeps must be >= 0");
+    if (x && nsweeps > 0 && !x->series) return fail(SQ_E_ARG, "null argument: the cluster sums need their series");
+    int rc = ens_cluster_state(e);
+    if (rc || nsweeps == 0) return rc;
+    DeviceGuard g(e->dev);
+    rc = ens_sync_recs(e);
+    if (!rc) rc = ens_cluster_bufs(e, nsweeps, bonds != nullptr, labels != nullptr, x);
+    if (rc) return rc;
+    for (int i = 0; i < nsweeps && !rc; ++i) rc = ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr, x);
+    const hipError_t he = hipStreamSynchronize(e->stream);
+    if (rc) return rc;
+    SQ_HIP(he);
+    return ens_cluster_end(e, nsweeps, bonds, labels, x);
+}
+
+// sq_phi4_ens_step_hmc_cluster and, x non-null, its _improved form.
+int ens_hmc_cluster(sq_phi4_ens *e, int nrounds, const EnsHmc &h, unsigned char *bonds, int *labels,
+                    const EnsSums *x) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    int rc = ens_hmc_fused_check(nrounds, h);
+    if (!rc && x && nrounds > 0 && !x->series)
+        rc = fail(SQ_E_ARG, "null argument: the cluster sums need their series");
+    if (!rc) rc = ens_cluster_state(e);  // the trajectories' C != 0 as well
+    if (rc || nrounds == 0) return rc;
+    DeviceGuard g(e->dev);
+    rc = ens_hmc_prepare(e, nrounds, h);
+    if (!rc) rc = ens_cluster_bufs(e, nrounds, bonds != nullptr, labels != nullptr, x);
+    if (!rc)
+        rc = ens_hmc_rounds(e, nrounds, h,
+                            [&](int i) { return ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr, x); });
+    if (!rc) rc = ens_cluster_end(e, nrounds, bonds, labels, x);
+    if (rc) return rc;
+    ens_advance(e, (unsigned long long)nrounds * (unsigned long long)h.ntraj);  // one count per trajectory
     return SQ_OK;
 }
 
@@ -390,38 +467,27 @@ int sq_phi4_ens_set_cluster_sweep(sq_phi4_ens *e, unsigned long long c) {
 }
 
 int sq_phi4_ens_cluster(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels) {
-    if (!e) return fail(SQ_E_ARG, "null ensemble");
-    if (nsweeps < 0) return fail(SQ_E_ARG, "nsweeps must be >= 0");
-    int rc = ens_cluster_state(e);
-    if (rc || nsweeps == 0) return rc;
-    DeviceGuard g(e->dev);
-    rc = ens_sync_recs(e);
-    if (!rc) rc = ens_cluster_bufs(e, nsweeps, bonds != nullptr, labels != nullptr);
-    if (rc) return rc;
-    for (int i = 0; i < nsweeps && !rc; ++i) rc = ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr);
-    const hipError_t he = hipStreamSynchronize(e->stream);
-    if (rc) return rc;
-    SQ_HIP(he);
-    return ens_cluster_end(e, nsweeps, bonds, labels);
+    return ens_cluster(e, nsweeps, bonds, labels, nullptr);
+}
+
+int sq_phi4_ensemble_cluster_improved(sq_phi4_ens *e, int nsweeps, double *series, unsigned char *bonds, int *labels,
+                                 long long *weights) {
+    const EnsSums x{series, weights};
+    return ens_cluster(e, nsweeps, bonds, labels, &x);
 }
 
 int sq_phi4_ens_step_hmc_cluster(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
                                  double *series, int measure, double *rec_hmc, unsigned char *bonds, int *labels) {
-    if (!e) return fail(SQ_E_ARG, "null ensemble");
     const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
-    int rc = ens_hmc_fused_check(nrounds, h);
-    if (!rc) rc = ens_cluster_state(e);  // the trajectories' C != 0 as well
-    if (rc || nrounds == 0) return rc;
-    DeviceGuard g(e->dev);
-    rc = ens_hmc_prepare(e, nrounds, h);
-    if (!rc) rc = ens_cluster_bufs(e, nrounds, bonds != nullptr, labels != nullptr);
-    if (!rc)
-        rc = ens_hmc_rounds(e, nrounds, h,
-                            [&](int i) { return ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr); });
-    if (!rc) rc = ens_cluster_end(e, nrounds, bonds, labels);
-    if (rc) return rc;
-    ens_advance(e, (unsigned long long)nrounds * (unsigned long long)ntraj);  // one count per trajectory
-    return SQ_OK;
+    return ens_hmc_cluster(e, nrounds, h, bonds, labels, nullptr);
+}
+
+int sq_phi4_ensemble_step_hmc_cluster_improved(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                          double *series, int measure, double *rec_hmc, unsigned char *bonds,
+                                          int *labels, double *cseries, long long *weights) {
+    const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
+    const EnsSums x{cseries, weights};
+    return ens_hmc_cluster(e, nrounds, h, bonds, labels, &x);
 }
 
 int sq_phi4_ens_cluster_stats(sq_phi4_ens *e, int first, int count, long long *out) {
@@ -440,6 +506,18 @@ int sq_phi4_ens_cluster_shape_info(const int dims[3], int out[4]) {
     out[1] = s.T;
     out[2] = s.mom_lds_bytes;
     out[3] = sq::kPhi4EnsLdsBytes;
+    return SQ_OK;
+}
+
+int sq_phi4_ensemble_cluster_improved_shape_info(const int dims[3], int out[5]) {
+    int rc = ens_shape_dims(dims, out);
+    if (rc) return rc;
+    const sq::Phi4EnsClusterSumShape s = sq::phi4_ens_cluster_sum_shape(dims[0] * dims[1] * dims[2]);
+    out[0] = s.K;
+    out[1] = s.T;
+    out[2] = s.lds_bytes;
+    out[3] = sq::kPhi4EnsLdsBytes;
+    out[4] = s.park;
     return SQ_OK;
 }
 

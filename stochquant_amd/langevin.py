@@ -1064,6 +1064,119 @@ class Phi4Ensemble:
                   labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
         return (ser, rh, bonds, labels) if record else ser
 
+    def _cluster_weights(self, n, record):
+        sites = self.shape[0] * self.shape[1] * self.shape[2]
+        return np.zeros((n, self.R, sites, 7), dtype=np.int64) if record else None
+
+    def cluster_improved(self, sweeps=1, record=False):
+        """`cluster(sweeps)` with the cluster sums of the improved estimators
+        (sq_phi4_ensemble_cluster_improved; include/stochquant.h has the
+        definition): fields, counters and statistics are bit for bit those of
+        `cluster`.  Returns the (sweeps, R, 8) series I2, I4, F_x, F_y, F_z,
+        Mmax, Mtot, nsat per replica and sweep: with M_C = Σ_{i∈C} |φ_i|,
+        I2 = Σ_C M_C² and I4 = Σ_C M_C⁴ give ⟨(Σφ)²⟩ = ⟨I2⟩ and ⟨(Σφ)⁴⟩ =
+        ⟨3 I2² − 2 I4⟩, and F_µ = Σ_C |Σ_{i∈C} |φ_i| e^{ip·x_i}|² at the unit
+        momentum of axis µ gives ⟨|Σφ e^{ip·x}|²⟩ (`cluster_observables` turns
+        the series into χ, the Binder cumulant and ξ_2nd).  Sites with |φ| ≥
+        2¹⁵, ∞ or NaN weigh nothing and are counted in nsat.  record=True:
+        returns (series, bonds, labels, weights), weights the (sweeps, R,
+        sites, 7) int64 sums M, A_x, B_x, A_y, B_y, A_z, B_z (fixed point, 32
+        fractional bits) at each cluster's root, 0 elsewhere.
+
+        A call of its own rather than a keyword of `cluster`: the signatures
+        of `cluster` and `step_hmc_cluster` are pinned by their tests."""
+        sweeps = int(sweeps)
+        n = max(sweeps, 0)
+        ser = np.zeros((n, self.R, 8))
+        bonds, labels = self._cluster_records(n, record)
+        weights = self._cluster_weights(n, record)
+        _lib.call("sq_phi4_ensemble_cluster_improved", self._h, sweeps, _dptr(ser) if ser.size else None,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None,
+                  weights.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)) if record and weights.size else None)
+        return (ser, bonds, labels, weights) if record else ser
+
+    def step_hmc_cluster_improved(self, rounds, ntraj=1, nleap=1, randomize=False, every=0, correlate=False,
+                                  record=False):
+        """`step_hmc_cluster` with every round's sweep a `cluster_improved`
+        sweep (sq_phi4_ensemble_step_hmc_cluster_improved), bit for bit the loop of
+        `step_hmc` and `cluster_improved(1)`.  Returns (series, cseries), series
+        as `step_hmc_cluster` returns it (None without `every`) and cseries the
+        (rounds, R, 8) cluster series; record=True: (series, rec_hmc, bonds,
+        labels, cseries, weights)."""
+        rounds, ntraj, nleap, every = int(rounds), int(ntraj), int(nleap), int(every)
+        if nleap < 1 or nleap > 4096:
+            raise ValueError("step_hmc_cluster_improved: nleap must lie in [1, 4096]")
+        if correlate and every < 1:
+            raise ValueError("step_hmc_cluster_improved: correlate=True needs every >= 1")
+        if every > 0 and ntraj % every != 0:
+            raise ValueError("step_hmc_cluster_improved: every must divide ntraj")
+        nr, nj = max(rounds, 0), max(ntraj, 0)
+        ser = np.zeros((nr * (nj // every), self.R, 4)) if every > 0 else None
+        rh = np.zeros((nr * nj, self.R, 4)) if record else None
+        cser = np.zeros((nr, self.R, 8))
+        bonds, labels = self._cluster_records(nr, record)
+        weights = self._cluster_weights(nr, record)
+        _lib.call("sq_phi4_ensemble_step_hmc_cluster_improved", self._h, rounds, ntraj, nleap, 1 if randomize else 0, every,
+                  _dptr(ser) if ser is not None and ser.size else None, 1 if correlate else 0,
+                  _dptr(rh) if rh is not None and rh.size else None,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None,
+                  _dptr(cser) if cser.size else None,
+                  weights.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)) if record and weights.size else None)
+        return (ser, rh, bonds, labels, cser, weights) if record else (ser, cser)
+
+    @staticmethod
+    def cluster_observables(cseries, shape, axis_mask=None):
+        """The finite-size-scaling observables of a (sweeps, R, 8) cluster
+        series of lattices of `shape`, over sweeps and replicas, each as
+        (value, standard error): "chi" = ⟨M²⟩ / V from I2, "binder" = 1 −
+        ⟨M⁴⟩ / (3 ⟨M²⟩²) with ⟨M⁴⟩ = ⟨3 I2² − 2 I4⟩, and "xi" = one pair per
+        axis of `axis_mask` (default: all three), ξ_2nd = sqrt((⟨I2⟩ / ⟨F_µ⟩ −
+        1) / (4 sin²(π / L_µ))).  The errors come from the scatter of the
+        replicas (a jackknife over them: the plain standard error of the
+        replica means for χ); they need R ≥ 2.  Unconverged sweeps (nsat < 0)
+        are left out."""
+        s = np.asarray(cseries, dtype=np.float64)
+        if s.ndim != 3 or s.shape[2] != 8 or s.shape[1] < 2 or s.shape[0] < 1:
+            raise ValueError("cluster_observables: a (sweeps >= 1, R >= 2, 8) series is needed")
+        mask = [True] * 3 if axis_mask is None else [bool(m) for m in axis_mask]
+        if len(mask) != 3:
+            raise ValueError("cluster_observables: axis_mask holds one entry per axis x, y, z")
+        ok = s[:, :, 7] >= 0
+        if not ok.any(axis=0).all():
+            raise ValueError("cluster_observables: a replica has no converged sweep")
+        w = ok / ok.sum(axis=0, keepdims=True)
+        q = np.stack([s[:, :, 0], 3.0 * s[:, :, 0] ** 2 - 2.0 * s[:, :, 1], s[:, :, 2], s[:, :, 3], s[:, :, 4]], axis=2)
+        per = (q * w[:, :, None]).sum(axis=0)               # (R, 5) replica means
+        V = float(shape[0] * shape[1] * shape[2])
+
+        def f(m):
+            out = [m[0] / V, 1.0 - m[1] / (3.0 * m[0] * m[0])]
+            for mu in range(3):
+                if mask[mu]:
+                    x = (m[0] / m[2 + mu] - 1.0) / (4.0 * np.sin(np.pi / shape[mu]) ** 2)
+                    out.append(np.sqrt(x) if x >= 0 else np.nan)
+            return np.asarray(out)
+
+        R = per.shape[0]
+        full = f(per.mean(axis=0))
+        jk = np.stack([f((per.sum(axis=0) - per[r]) / (R - 1)) for r in range(R)])
+        err = np.sqrt((R - 1) / R * ((jk - jk.mean(axis=0)) ** 2).sum(axis=0))
+        pairs = [(float(v), float(e)) for v, e in zip(full, err)]
+        return {"chi": pairs[0], "binder": pairs[1], "xi": pairs[2:]}
+
+    @staticmethod
+    def cluster_improved_shape_info(shape):
+        """What the sweep with the cluster sums asks for, without a device: K, T,
+        dynamic LDS bytes, the LDS limit, and "park": 1 where a lane's labels
+        wait in device memory while the LDS image serves as the accumulators
+        (K = 8), 0 where they wait in registers."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 5)()
+        _lib.call("sq_phi4_ensemble_cluster_improved_shape_info", dims, out)
+        return dict(zip(("K", "T", "lds_bytes", "lds_limit", "park"), (int(v) for v in out)))
+
     def cluster_stats(self, first=0, count=None):
         """(count, 5) int64: sweeps, clusters, flipped clusters, flipped sites
         and unconverged sweeps (always 0: the labelling's pass bound is its
