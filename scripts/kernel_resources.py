@@ -18,9 +18,10 @@ KEYS = ("VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize", "VGPRs Spill", "Occupancy
 
 def resources(src, extra=()):
     sys.path.insert(0, ROOT)
-    from stochquant_amd.build import COMMON, EXTRA_FLAGS, HIPCC, ARCH
-    cmd = [HIPCC] + COMMON + EXTRA_FLAGS.get(os.path.basename(src), []) + [f"--offload-arch={ARCH}", "-x", "hip", "-c", src, "-o", os.devnull,
-                              "-Rpass-analysis=kernel-resource-usage"] + list(extra)
+    from stochquant_amd.build import compile_command
+    # the flags of the source of that name in the build (a copy elsewhere is compiled as the source it copies)
+    cmd = compile_command(os.path.basename(src), src) + ["-o", os.devnull,
+                                                         "-Rpass-analysis=kernel-resource-usage"] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise SystemExit(r.stderr[-4000:])

@@ -35,17 +35,20 @@ HOST_SOURCES = ["sq_core.cpp", "sq_comm.cpp", "sq_phi4_create.cpp", "sq_phi4_pla
                 "sq_phi4_frames.cpp", "sq_phi4_fields.cpp", "sq_qm1d_host.cpp", "sq_ens.cpp", "sq_phi4_ens.cpp",
                 "sq_phi4_ens_frames.cpp", "sq_phi4_ens_corr.cpp", "sq_phi4_ens_flow.cpp", "sq_phi4_ens_samplers.cpp",
                 "sq_diag.cpp", "sq_io.cpp"]
-HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_buf.h", "sq_phi4_ens_host.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h", "sq_phi4_ens_flow_dev.h", "sq_phi4_ens_mala_dev.h",
+HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_buf.h", "sq_phi4_ens_host.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h",
            "sq_qm1d_math.h"]
-# device sources that include another one
-INCLUDES = {"sq_phi4_run.hip": ["sq_phi4.hip"], "sq_phi4_ens.hip": ["sq_phi4.hip"],
-            "sq_phi4_ens_flow.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_flow_frames.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_mala.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_hmc.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_exchange.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_cluster.hip": ["sq_phi4_ens.hip", "sq_phi4.hip"],
-            "sq_phi4_ens_cluster_improved.hip": ["sq_phi4_ens_cluster.hip", "sq_phi4_ens.hip", "sq_phi4.hip"]}
+# per device source, the project's device files it includes, directly or through one of them: other device
+# sources, the *_dev.h device headers and the ensemble's launch header (tests/test_build_table.py scans the
+# sources and holds this table to them)
+_ENS = ["sq_phi4_ens_dev.h", "sq_phi4_ens_launch.h", "sq_phi4.hip"]
+INCLUDES = {"sq_phi4_run.hip": ["sq_phi4.hip"], "sq_phi4_ens.hip": _ENS,
+            "sq_phi4_ens_flow.hip": ["sq_phi4_ens_flow_dev.h"] + _ENS,
+            "sq_phi4_ens_flow_frames.hip": ["sq_phi4_ens_flow_dev.h"] + _ENS,
+            "sq_phi4_ens_mala.hip": ["sq_phi4_ens_mala_dev.h"] + _ENS,
+            "sq_phi4_ens_hmc.hip": ["sq_phi4_ens_mala_dev.h"] + _ENS,
+            "sq_phi4_ens_exchange.hip": _ENS,
+            "sq_phi4_ens_cluster.hip": ["sq_phi4_ens_cluster_dev.h"] + _ENS,
+            "sq_phi4_ens_cluster_improved.hip": ["sq_phi4_ens_cluster_dev.h"] + _ENS}
 # per-source flags beside COMMON.  sq_phi4_ens_mala.hip: the step loop calls the double exp once per step, and
 # machine LICM hoists the twenty-odd 64-bit constants of its polynomial out of the loop into vector registers,
 # where they stay for the whole call: the K = 8 instances then spill to private memory.  The kernels of that file
@@ -55,6 +58,13 @@ EXTRA_FLAGS = {"sq_phi4_ens_mala.hip": ["-mllvm", "-disable-machine-licm"],
                "sq_phi4_ens_hmc.hip": ["-mllvm", "-disable-machine-licm"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-Wall",
           "-Wno-unused-function"]
+
+
+def compile_command(src, path=None):
+    """The compile line of device or host source `src` (a name of DEVICE_SOURCES / HOST_SOURCES), without its
+    output: COMMON, the source's EXTRA_FLAGS, the arch.  path: compile that file in its place (a variant)."""
+    return [HIPCC] + COMMON + EXTRA_FLAGS.get(src, []) + [f"--offload-arch={ARCH}", "-x", "hip", "-c",
+                                                         path or os.path.join(CSRC, src)]
 
 
 def _digest(paths, extra):
@@ -95,12 +105,12 @@ def build(force=False, verbose=False):
     for src in DEVICE_SOURCES + HOST_SOURCES:
         s = os.path.join(CSRC, src)
         o = os.path.join(OBJ, src + ".o")
-        flags = COMMON + EXTRA_FLAGS.get(src, []) + [f"--offload-arch={ARCH}", "-x", "hip"]
+        cmd = compile_command(src)
         stamp = o + ".sha"
-        dig = _digest([s] + [os.path.join(CSRC, d) for d in INCLUDES.get(src, [])] + hdrs, flags)
+        dig = _digest([s] + [os.path.join(CSRC, d) for d in INCLUDES.get(src, [])] + hdrs, cmd[1:-2])
         if not force and os.path.exists(o) and os.path.exists(stamp) and open(stamp).read() == dig:
             continue
-        jobs.append(([HIPCC] + flags + ["-c", s, "-o", o], stamp, dig))
+        jobs.append((cmd + ["-o", o], stamp, dig))
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 4)) as ex:
         for (cmd, stamp, dig), _ in zip(jobs, ex.map(lambda j: _run(j[0]), jobs)):
             with open(stamp, "w") as fh:

@@ -233,11 +233,12 @@ int sq_phi4_ens_shape_info(const int dims[3], int out[8]) {
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
     out[0] = s.K;
     out[1] = s.T;
-    out[2] = s.two ? 2 : 1;
-    out[3] = s.lds_bytes;
-    out[4] = s.fr_two ? 2 : 1;
-    out[5] = s.fr_lds_bytes;
-    out[6] = s.mom_lds_bytes;
+    const sq::Phi4EnsLds st = s.lds(sq::kPhi4EnsLdsStep), fr = s.lds(sq::kPhi4EnsLdsFrames);
+    out[2] = st.images;
+    out[3] = st.bytes;
+    out[4] = fr.images;
+    out[5] = fr.bytes;
+    out[6] = s.lds(sq::kPhi4EnsLdsStored).bytes;
     out[7] = sq::kPhi4EnsLdsBytes;
     return SQ_OK;
 }

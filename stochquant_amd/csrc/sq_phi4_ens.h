@@ -89,33 +89,37 @@ struct Phi4EnsPCorrArgs {
     Phi4EnsCorrArgs corr;    // nullable (G == nullptr)
 };
 
+// The dynamic LDS of a launch: the image(s) of the lattice, the launch's
+// scratch, then what the launch's measurement keeps behind the scratch.  One
+// rule for every launch: two images (one barrier per step instead of two)
+// exactly when they fit in kPhi4EnsLdsBytes with the rest, and never for a
+// launch that works on the stored field.
+enum Phi4EnsLdsKind {
+    kPhi4EnsLdsStep,    // the step launches of every sampler: kPhi4EnsScratchBytes behind the image(s)
+    kPhi4EnsLdsFrames,  // the frames launches: kPhi4EnsFrameScratchBytes
+    kPhi4EnsLdsStored   // moments, slices, pslices, exchange, cluster: one image, kPhi4EnsScratchBytes
+};
+// The bytes behind the scratch: none without a measurement, else ...
+constexpr int phi4_ens_corr_bytes(int Lz) { return 8 * Lz; }    // ens_corr: Lz doubles, the slice sums
+// ens_pcorr: 2 Lz doubles (S, then each momentum's A and B in turn: the need does not depend on their number)
+constexpr int phi4_ens_pcorr_bytes(int Lz) { return 16 * Lz; }
+constexpr int kPhi4EnsClusterSumBytes = 4 * 8;                  // the cluster sums: the per-weight totals
+struct Phi4EnsLds {
+    int images, bytes;
+};
+inline Phi4EnsLds phi4_ens_lds(int sites, Phi4EnsLdsKind kind, int behind = 0) {
+    const int rest = (kind == kPhi4EnsLdsFrames ? kPhi4EnsFrameScratchBytes : kPhi4EnsScratchBytes) + behind;
+    const int images = kind != kPhi4EnsLdsStored && 2 * 4 * sites + rest <= kPhi4EnsLdsBytes ? 2 : 1;
+    return Phi4EnsLds{images, images * 4 * sites + rest};
+}
+
 // Work-group shape of a lattice of `sites` sites (a multiple of 8): K float4
-// quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024), and per
-// launch whether two LDS images fit (one barrier per step instead of two) and
-// the dynamic LDS it asks for: the image(s), then the launch's scratch.  The
-// three launchers and sq_phi4_ens_shape_info take every number from here.
+// quads per lane (1, 2, 4 or 8), T lanes (a multiple of 64, <= 1024).  Every
+// launcher and every *_shape_info entry point asks lds() for its layout.
 struct Phi4EnsShape {
-    int K, T;
-    bool two;           // the step launch
-    int lds_bytes;
-    bool fr_two;        // the frames launch (kPhi4EnsFrameScratchBytes behind the images)
-    int fr_lds_bytes;
-    int mom_lds_bytes;  // the moments launch: always one image
-    // the correlator launches (Lz > 0): the same layouts with Lz doubles, the slice sums, behind the
-    // launch's scratch; a shape with two images in the plain launch may have one here
-    bool co_two;        // the step launch with the correlator
-    int co_lds_bytes;
-    bool co_fr_two;     // the frames launch with the correlator
-    int co_fr_lds_bytes;
-    int sl_lds_bytes;   // the slices launch: one image, the scratch, the slice sums
-    // the momentum launches (Lz > 0): the correlator launches' layouts with 2 Lz doubles behind the scratch
-    // (S, then each momentum's A and B in turn: the need does not depend on the number of momenta)
-    bool pc_ok;         // one image fits in all three launches: the shape can hold momenta
-    bool pc_two;        // the step launch with momenta
-    int pc_lds_bytes;
-    bool pc_fr_two;     // the frames launch with momenta
-    int pc_fr_lds_bytes;
-    int pc_sl_lds_bytes;  // the pslices launch: one image, the scratch, the projections
+    int K, T, sites;
+    bool pc_ok;  // Lz > 0 and one image fits in the step, frames and pslices launches with momenta
+    Phi4EnsLds lds(Phi4EnsLdsKind kind, int behind = 0) const { return phi4_ens_lds(sites, kind, behind); }
 };
 Phi4EnsShape phi4_ens_shape(int sites, int Lz = 0);
 
@@ -211,18 +215,11 @@ struct Phi4EnsFlowArgs {
     long long *nmeas;   // [R][nlev]
 };
 
-// What the flow launches ask for, from phi4_ens_shape: the step launch keeps the plain launch's layout without
-// the correlator and the correlator launch's with it, the flowed launch takes the latter, the flow-field launch
-// the former.  stash: where the lane's quads wait during a flow inside the step kernel, 0 registers, 1 the
-// replica's row of the field in device memory (K = 8: no 32 registers to spare).
-struct Phi4EnsFlowShape {
-    int K, T;
-    bool two;
-    int lds_bytes;
-    bool co_two;
-    int co_lds_bytes;
-    bool fl_two;       // the flowed launch
-    int fl_lds_bytes;
+// What the flow launches ask for beside phi4_ens_shape: the step launch keeps the step launches' layout without
+// the correlator and with it, the flowed launch takes the latter, the flow-field launch the former.  stash:
+// where the lane's quads wait during a flow inside the step kernel, 0 registers, 1 the replica's row of the
+// field in device memory (K = 8: no 32 registers to spare).
+struct Phi4EnsFlowShape : Phi4EnsShape {
     int stash;
 };
 Phi4EnsFlowShape phi4_ens_flow_shape(int sites, int Lz);
@@ -244,21 +241,12 @@ hipError_t phi4_ens_flow_field_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArg
                                       int nsteps, float *out, hipStream_t s);
 
 // ---- flow measurements in frames and Heun steps (sq_phi4_ens_flow_frames.hip) ----
-// What those launches ask for, from phi4_ens_shape.  The frames launches of both schemes keep the frames launch's
-// layout without the correlator and the correlator frames launch's with it; the Heun step launch keeps the step
-// launches' as phi4_ens_step_flow_launch does.  *_stash: where the un-flowed field waits, 0 registers, 1 the
-// replica's row of the field in device memory.  mask: bit 2 scheme + corr set when the frames launch of that
-// scheme (0 Euler, 1 Heun) and correlator choice runs on the shape.
-struct Phi4EnsFramesFlowShape {
-    int K, T;
-    bool fr_two;          // the frames launches without the correlator
-    int fr_lds_bytes;
-    bool co_fr_two;       // ... with it
-    int co_fr_lds_bytes;
-    bool hs_two;          // the Heun step launch without the correlator
-    int hs_lds_bytes;
-    bool co_hs_two;       // ... with it
-    int co_hs_lds_bytes;
+// What those launches ask for beside phi4_ens_shape.  The frames launches of both schemes keep the frames
+// launches' layout without the correlator and with it; the Heun step launch keeps the step launches' as
+// phi4_ens_step_flow_launch does.  *_stash: where the un-flowed field waits, 0 registers, 1 the replica's row of
+// the field in device memory.  mask: bit 2 scheme + corr set when the frames launch of that scheme (0 Euler,
+// 1 Heun) and correlator choice runs on the shape.
+struct Phi4EnsFramesFlowShape : Phi4EnsShape {
     int fr_stash, hfr_stash, hs_stash;  // Euler frames, Heun frames, Heun steps
     int mask;
 };
@@ -336,10 +324,9 @@ struct Phi4EnsClusterSumArgs {
                          // them (device memory); else not used
 };
 // Where the labels wait while the image serves as the accumulators: the lane's registers (K <= 4) or device
-// memory (K = 8: no 32 registers to spare).  The work-group shape is the plain sweep's, the LDS 32 bytes more.
-struct Phi4EnsClusterSumShape {
-    int K, T;
-    int lds_bytes;
+// memory (K = 8: no 32 registers to spare).  The work-group shape is the plain sweep's, the LDS
+// kPhi4EnsClusterSumBytes more.
+struct Phi4EnsClusterSumShape : Phi4EnsShape {
     int park;  // 0 registers, 1 device memory
 };
 Phi4EnsClusterSumShape phi4_ens_cluster_sum_shape(int sites);

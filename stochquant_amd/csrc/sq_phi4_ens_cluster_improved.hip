@@ -1,19 +1,15 @@
 // sq_phi4_ens_cluster_improved.hip -- the Swendsen-Wang sweep of sq_phi4_ens_cluster.hip with the cluster sums
-// of the improved estimators (include/stochquant.h): the second kind of instance of that file's
-// kernel template, phi4_ens_cluster_kernel<K, Phi4EnsClusterSumArgs>, in a translation unit of its own.  The
-// kernel's comment in sq_phi4_ens_cluster.hip describes the limb passes.
-#define SQ_PHI4_ENS_CLUSTER_KERNEL_ONLY
-#include "sq_phi4_ens_cluster.hip"
+// of the improved estimators (include/stochquant.h): the second kind of instance of the kernel
+// template of sq_phi4_ens_cluster_dev.h, phi4_ens_cluster_kernel<K, Phi4EnsClusterSumArgs>, in a translation unit
+// of its own.  The kernel's comment there describes the limb passes.
+#include "sq_phi4_ens_cluster_dev.h"
+#include "sq_phi4_ens_launch.h"
 
 namespace sq {
 
 Phi4EnsClusterSumShape phi4_ens_cluster_sum_shape(int sites) {
-    const Phi4EnsShape sh = phi4_ens_shape(sites);
-    Phi4EnsClusterSumShape s;
-    s.K = sh.K;
-    s.T = sh.T;
-    s.lds_bytes = sh.mom_lds_bytes + 4 * 8;  // the per-weight totals behind the scratch
-    s.park = sh.K == 8 ? 1 : 0;  // the kernel's PARK
+    Phi4EnsClusterSumShape s{phi4_ens_shape(sites), 0};
+    s.park = s.K == 8 ? 1 : 0;  // the kernel's PARK
     return s;
 }
 
@@ -27,13 +23,8 @@ hipError_t phi4_ens_cluster_improved_launch(const Phi4EnsArgs &a, const Phi4EnsC
     Phi4EnsClusterArgs wq = w;
     Phi4EnsClusterSumArgs xq = x;
     void *args[] = {&q, &wq, &xq};
-    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_cluster_kernel<1, Phi4EnsClusterSumArgs>
-                     : sh.K == 2 ? (const void *)&phi4_ens_cluster_kernel<2, Phi4EnsClusterSumArgs>
-                     : sh.K == 4 ? (const void *)&phi4_ens_cluster_kernel<4, Phi4EnsClusterSumArgs>
-                                 : (const void *)&phi4_ens_cluster_kernel<8, Phi4EnsClusterSumArgs>;
-    hipError_t e = ens_lds_attr(fn, sh.lds_bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)sh.lds_bytes, s);
+    return ens_launch(SQ_ENS_KERNEL(sh.K, phi4_ens_cluster_kernel, Phi4EnsClusterSumArgs), nrep, sh.T,
+                      sh.lds(kPhi4EnsLdsStored, kPhi4EnsClusterSumBytes).bytes, args, s);
 }
 
 }  // namespace sq

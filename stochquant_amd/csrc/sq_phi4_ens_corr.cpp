@@ -245,11 +245,13 @@ int sq_phi4_ens_pcorr_shape_info(const int dims[3], int out[6]) {
     if (rc) return rc;
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
     if (!s.pc_ok) return fail(SQ_E_ARG, "the lattice shape leaves no LDS for the momentum projections (16 Lz bytes)");
-    out[0] = s.pc_two ? 2 : 1;
-    out[1] = s.pc_lds_bytes;
-    out[2] = s.pc_fr_two ? 2 : 1;
-    out[3] = s.pc_fr_lds_bytes;
-    out[4] = s.pc_sl_lds_bytes;
+    const int pl = sq::phi4_ens_pcorr_bytes(dims[2]);
+    const sq::Phi4EnsLds st = s.lds(sq::kPhi4EnsLdsStep, pl), fr = s.lds(sq::kPhi4EnsLdsFrames, pl);
+    out[0] = st.images;
+    out[1] = st.bytes;
+    out[2] = fr.images;
+    out[3] = fr.bytes;
+    out[4] = s.lds(sq::kPhi4EnsLdsStored, pl).bytes;
     out[5] = dims[2] / 2 + 1;
     return SQ_OK;
 }
@@ -258,11 +260,13 @@ int sq_phi4_ens_corr_shape_info(const int dims[3], int out[6]) {
     int rc = ens_shape_dims(dims, out);
     if (rc) return rc;
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
-    out[0] = s.co_two ? 2 : 1;
-    out[1] = s.co_lds_bytes;
-    out[2] = s.co_fr_two ? 2 : 1;
-    out[3] = s.co_fr_lds_bytes;
-    out[4] = s.sl_lds_bytes;
+    const int sl = sq::phi4_ens_corr_bytes(dims[2]);
+    const sq::Phi4EnsLds st = s.lds(sq::kPhi4EnsLdsStep, sl), fr = s.lds(sq::kPhi4EnsLdsFrames, sl);
+    out[0] = st.images;
+    out[1] = st.bytes;
+    out[2] = fr.images;
+    out[3] = fr.bytes;
+    out[4] = s.lds(sq::kPhi4EnsLdsStored, sl).bytes;
     out[5] = dims[2] / 2 + 1;
     return SQ_OK;
 }

@@ -29,8 +29,8 @@
 // depend on them), so the stores cannot overtake a read of the same row.
 // 2 K float4 of field per lane: 64 registers at K = 8.  No atomics: every word
 // has one writer.
-#define SQ_PHI4_ENS_KERNELS_ONLY
-#include "sq_phi4_ens.hip"
+#include "sq_phi4_ens_dev.h"
+#include "sq_phi4_ens_launch.h"
 
 namespace sq {
 
@@ -146,17 +146,11 @@ hipError_t phi4_ens_exchange_launch(const Phi4EnsArgs &a, const Phi4EnsXchgArgs 
     const int np = phi4_ens_xchg_pairs(w.nlad, w.x);
     if (np == 0) return hipSuccess;  // nlad = 2, odd round
     const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz);
-    const int bytes = sh.mom_lds_bytes;
     Phi4EnsArgs q = a;
     Phi4EnsXchgArgs wq = w;
     void *args[] = {&q, &wq};
-    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_exchange_kernel<1>
-                     : sh.K == 2 ? (const void *)&phi4_ens_exchange_kernel<2>
-                     : sh.K == 4 ? (const void *)&phi4_ens_exchange_kernel<4>
-                                 : (const void *)&phi4_ens_exchange_kernel<8>;
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)((nrep / w.nlad) * np)), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    return ens_launch(SQ_ENS_KERNEL(sh.K, phi4_ens_exchange_kernel), (nrep / w.nlad) * np, sh.T,
+                      sh.lds(kPhi4EnsLdsStored).bytes, args, s);
 }
 
 }  // namespace sq

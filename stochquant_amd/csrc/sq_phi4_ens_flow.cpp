@@ -233,11 +233,13 @@ int sq_phi4_ens_flow_shape_info(const int dims[3], int out[6]) {
     int rc = ens_shape_dims(dims, out);
     if (rc) return rc;
     const sq::Phi4EnsFlowShape s = sq::phi4_ens_flow_shape(dims[0] * dims[1] * dims[2], dims[2]);
-    out[0] = s.two ? 2 : 1;
-    out[1] = s.lds_bytes;
-    out[2] = s.co_two ? 2 : 1;
-    out[3] = s.co_lds_bytes;
-    out[4] = s.fl_lds_bytes;
+    const sq::Phi4EnsLds st = s.lds(sq::kPhi4EnsLdsStep);
+    const sq::Phi4EnsLds co = s.lds(sq::kPhi4EnsLdsStep, sq::phi4_ens_corr_bytes(dims[2]));
+    out[0] = st.images;
+    out[1] = st.bytes;
+    out[2] = co.images;
+    out[3] = co.bytes;
+    out[4] = co.bytes;  // the flowed launch takes the correlator launch's layout
     out[5] = s.stash;
     return SQ_OK;
 }

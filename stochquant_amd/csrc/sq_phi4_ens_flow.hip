@@ -5,8 +5,8 @@
 // false>, applied to a copy of its field with the replica's flow coefficients
 // (Phi4EnsFlowRec: the flow step as h, the flow's m² and λ, sig = 0): bit for
 // bit what a C = 0 ensemble gives after upload and step.  The measurements at a
-// level are that file's too: ens_sums + ens_fold, ens_corr.  This translation
-// unit includes sq_phi4_ens.hip for those device functions and restates none.
+// level are the ensemble's too: ens_sums + ens_fold, ens_corr.  This translation
+// unit takes those device functions from sq_phi4_ens_dev.h and restates none.
 //
 // phi4_ens_step_flow_kernel is phi4_ens_step_kernel's loop.  At a measurement
 // point -- behind the step's last barrier, cur holding the field the lane's
@@ -32,11 +32,9 @@
 //
 // The same measurement inside the frames kernels and the Heun step kernel is
 // sq_phi4_ens_flow_frames.hip; what the two files share (ens_flow_args,
-// ens_flow_step, ens_flow_measure, ens_flow_levels_ok) is sq_phi4_ens_flow_dev.h.
-#define SQ_PHI4_ENS_KERNELS_ONLY
-#include "sq_phi4_ens.hip"
-
-#include "sq_phi4_ens_flow_dev.h"  // ens_flow_args, ens_flow_step, ens_flow_measure, ens_flow_levels_ok
+// ens_flow_step, ens_flow_measure) is sq_phi4_ens_flow_dev.h.
+#include "sq_phi4_ens_flow_dev.h"  // ens_flow_args, ens_flow_step, ens_flow_measure
+#include "sq_phi4_ens_launch.h"
 
 namespace sq {
 
@@ -54,15 +52,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_step_flow_kernel(co
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
+    const Phi4StepArgs A = ens_step_args(rc, E.clampv);
     const bool nz = rc.sig != 0.0f;
     float *img0 = reinterpret_cast<float *>(ens_smem);
     float *img1 = two ? img0 + 4 * g.Q : img0;
@@ -209,87 +199,55 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_flow_field_kernel(c
         if (fl[j] & kEnsValid) of[(int)threadIdx.x + j * T] = c[j];
 }
 
-template <typename... CA>
-const void *ens_step_flow_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_step_flow_kernel<1, CA...>
-           : K == 2 ? (const void *)&phi4_ens_step_flow_kernel<2, CA...>
-           : K == 4 ? (const void *)&phi4_ens_step_flow_kernel<4, CA...>
-                    : (const void *)&phi4_ens_step_flow_kernel<8, CA...>;
-}
-
 }  // namespace
 
 Phi4EnsFlowShape phi4_ens_flow_shape(int sites, int Lz) {
-    const Phi4EnsShape sh = phi4_ens_shape(sites, Lz);
-    Phi4EnsFlowShape f;
-    f.K = sh.K;
-    f.T = sh.T;
-    f.two = sh.two;
-    f.lds_bytes = sh.lds_bytes;
-    f.co_two = sh.co_two;
-    f.co_lds_bytes = sh.co_lds_bytes;
-    f.fl_two = sh.co_two;
-    f.fl_lds_bytes = sh.co_lds_bytes;
-    f.stash = sh.K < 8 ? 0 : 1;  // phi4_ens_step_flow_kernel's REG
+    Phi4EnsFlowShape f{phi4_ens_shape(sites, Lz), 0};
+    f.stash = f.K < 8 ? 0 : 1;  // phi4_ens_step_flow_kernel's REG
     return f;
 }
 
 hipError_t phi4_ens_step_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, bool corr, int nrep,
                                      hipStream_t s) {
-    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < 1 || !ens_flow_levels_ok(w) ||
-        (a.series == nullptr && !corr) || (corr && (w.G == nullptr || w.S1 == nullptr || w.nmeas == nullptr)))
-        return hipErrorInvalidValue;
+    if (!ens_step_ok(a, nrep, true) || !ens_flow_ok(a, w, corr)) return hipErrorInvalidValue;
     const Phi4EnsFlowShape sh = phi4_ens_flow_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep, corr ? phi4_ens_corr_bytes(a.Lz) : 0);
     Phi4EnsArgs q = a;
     Phi4EnsFlowArgs wq = w;
     Phi4EnsCorrArgs cq{};
-    int two = (corr ? sh.co_two : sh.two) ? 1 : 0;
-    const int bytes = corr ? sh.co_lds_bytes : sh.lds_bytes;
+    int two = l.images == 2;
     void *args[] = {&q, &wq, &two, &cq};  // the plain instances take the first three
-    const void *fn = corr ? ens_step_flow_fn<Phi4EnsCorrArgs>(sh.K) : ens_step_flow_fn<>(sh.K);
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    const void *fn = corr ? SQ_ENS_KERNEL(sh.K, phi4_ens_step_flow_kernel, Phi4EnsCorrArgs)
+                          : SQ_ENS_KERNEL(sh.K, phi4_ens_step_flow_kernel);
+    return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
 }
 
 hipError_t phi4_ens_flowed_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, int first, int count, double *sums,
                                   double *S, double *g, hipStream_t s) {
-    if (!ens_shape_ok(a) || first < 0 || count < 1 || sums == nullptr || S == nullptr || g == nullptr ||
-        !ens_flow_levels_ok(w))
+    if (!ens_stored_ok(a, first, count) || sums == nullptr || S == nullptr || g == nullptr || !ens_flow_levels_ok(w))
         return hipErrorInvalidValue;
     const Phi4EnsFlowShape sh = phi4_ens_flow_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    // the flow steps ping-pong as a step launch's do: its layout with the correlator
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep, phi4_ens_corr_bytes(a.Lz));
     Phi4EnsArgs q = a;
     Phi4EnsFlowArgs wq = w;
-    int two = sh.fl_two ? 1 : 0;
-    const int bytes = sh.fl_lds_bytes;
+    int two = l.images == 2;
     void *args[] = {&q, &wq, &two, &first, &sums, &S, &g};
-    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_flowed_kernel<1>
-                     : sh.K == 2 ? (const void *)&phi4_ens_flowed_kernel<2>
-                     : sh.K == 4 ? (const void *)&phi4_ens_flowed_kernel<4>
-                                 : (const void *)&phi4_ens_flowed_kernel<8>;
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)count), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    return ens_launch(SQ_ENS_KERNEL(sh.K, phi4_ens_flowed_kernel), count, sh.T, l.bytes, args, s);
 }
 
 hipError_t phi4_ens_flow_field_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, int first, int count,
                                       int nsteps, float *out, hipStream_t s) {
-    if (!ens_shape_ok(a) || first < 0 || count < 1 || out == nullptr || w.rec == nullptr || nsteps < 0 ||
+    if (!ens_stored_ok(a, first, count) || out == nullptr || w.rec == nullptr || nsteps < 0 ||
         nsteps > kPhi4EnsMaxFlowSteps)
         return hipErrorInvalidValue;
     const Phi4EnsFlowShape sh = phi4_ens_flow_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep);  // the plain step launch's layout
     Phi4EnsArgs q = a;
     Phi4EnsFlowArgs wq = w;
-    int two = sh.two ? 1 : 0;
-    const int bytes = sh.lds_bytes;
+    int two = l.images == 2;
     void *args[] = {&q, &wq, &two, &first, &nsteps, &out};
-    const void *fn = sh.K == 1   ? (const void *)&phi4_ens_flow_field_kernel<1>
-                     : sh.K == 2 ? (const void *)&phi4_ens_flow_field_kernel<2>
-                     : sh.K == 4 ? (const void *)&phi4_ens_flow_field_kernel<4>
-                                 : (const void *)&phi4_ens_flow_field_kernel<8>;
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)count), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    return ens_launch(SQ_ENS_KERNEL(sh.K, phi4_ens_flow_field_kernel), count, sh.T, l.bytes, args, s);
 }
 
 }  // namespace sq

@@ -1,8 +1,9 @@
 // sq_phi4_ens_flow_dev.h -- the device functions the gradient-flow kernels
 // share (sq_phi4_ens_flow.hip, sq_phi4_ens_flow_frames.hip).
-// Included behind sq_phi4_ens.hip (SQ_PHI4_ENS_KERNELS_ONLY), whose ens_step,
-// ens_sums, ens_fold and ens_corr it calls; it restates none of them.
+// It calls ens_step, ens_sums, ens_fold and ens_corr of sq_phi4_ens_dev.h and
+// restates none of them.
 #pragma once
+#include "sq_phi4_ens_dev.h"
 
 namespace sq {
 
@@ -91,13 +92,6 @@ __device__ __forceinline__ void ens_flow_measure(const Phi4EnsArgs &E, const Phi
             }
         }
     }
-}
-
-bool ens_flow_levels_ok(const Phi4EnsFlowArgs &w) {
-    if (w.rec == nullptr || w.nlev < 1 || w.nlev > kPhi4EnsMaxFlowLevels) return false;
-    for (int l = 0; l < w.nlev; ++l)
-        if (w.lev[l] < (l ? w.lev[l - 1] + 1 : 0) || w.lev[l] > kPhi4EnsMaxFlowSteps) return false;
-    return true;
 }
 
 }  // namespace

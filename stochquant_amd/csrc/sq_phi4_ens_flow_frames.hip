@@ -9,7 +9,7 @@
 // the flow accumulators.  The three kernels here are phi4_ens_frames_kernel,
 // phi4_ens_heun_frames_kernel and phi4_ens_heun_kernel of sq_phi4_ens.hip, loop
 // for loop, with that measurement where theirs stand; this translation unit
-// includes that file for every device function and restates none.
+// takes every device function from sq_phi4_ens_dev.h and restates none.
 //
 // Where the un-flowed field waits (Phi4EnsFramesFlowShape's stash).  In the
 // frames kernels the measurement follows the frame's verdict, where the
@@ -26,10 +26,8 @@
 // scratch, the correlator the launch's slice region, W's accumulators and
 // E.series are the only device memory written.  The frames' record slots (fk,
 // fw) lie behind the scratch and are neither read nor written by it.
-#define SQ_PHI4_ENS_KERNELS_ONLY
-#include "sq_phi4_ens.hip"
-
 #include "sq_phi4_ens_flow_dev.h"
+#include "sq_phi4_ens_launch.h"
 
 namespace sq {
 
@@ -60,15 +58,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_frames_flow_kernel(
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
     const Phi4EnsFrameState st = F.st[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
+    Phi4StepArgs A = ens_step_args(rc, E.clampv);
     const bool nz = rc.sig != 0.0f;
     float *img0 = reinterpret_cast<float *>(ens_smem);
     float *img1 = two ? img0 + 4 * g.Q : img0;
@@ -271,15 +261,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_heun_frames_flow_ke
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
     const Phi4EnsFrameState st = F.st[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
+    Phi4StepArgs A = ens_step_args(rc, E.clampv);
     const bool nz = rc.sig != 0.0f;
     float *cur = reinterpret_cast<float *>(ens_smem);
     float *oth = TWO ? cur + 4 * g.Q : cur;
@@ -473,15 +455,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_heun_flow_kernel(co
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
+    const Phi4StepArgs A = ens_step_args(rc, E.clampv);
     const bool nz = rc.sig != 0.0f;  // phi4_step_launch's choice of instance
     float *cur = reinterpret_cast<float *>(ens_smem);
     float *oth = two ? cur + 4 * g.Q : cur;
@@ -556,101 +530,55 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_heun_flow_kernel(co
     if (am >= E.clampv) E.flags[r] = 1;
 }
 
-template <typename... CA>
-const void *ens_frames_flow_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_frames_flow_kernel<1, CA...>
-           : K == 2 ? (const void *)&phi4_ens_frames_flow_kernel<2, CA...>
-           : K == 4 ? (const void *)&phi4_ens_frames_flow_kernel<4, CA...>
-                    : (const void *)&phi4_ens_frames_flow_kernel<8, CA...>;
-}
-
-template <bool TWO, typename... CA>
-const void *ens_heun_frames_flow_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_heun_frames_flow_kernel<1, TWO, CA...>
-           : K == 2 ? (const void *)&phi4_ens_heun_frames_flow_kernel<2, TWO, CA...>
-           : K == 4 ? (const void *)&phi4_ens_heun_frames_flow_kernel<4, TWO, CA...>
-                    : (const void *)&phi4_ens_heun_frames_flow_kernel<8, TWO, CA...>;
-}
-
-template <typename... CA>
-const void *ens_heun_flow_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_heun_flow_kernel<1, CA...>
-           : K == 2 ? (const void *)&phi4_ens_heun_flow_kernel<2, CA...>
-           : K == 4 ? (const void *)&phi4_ens_heun_flow_kernel<4, CA...>
-                    : (const void *)&phi4_ens_heun_flow_kernel<8, CA...>;
-}
-
 }  // namespace
 
 Phi4EnsFramesFlowShape phi4_ens_frames_flow_shape(int sites, int Lz) {
-    const Phi4EnsShape sh = phi4_ens_shape(sites, Lz);
-    Phi4EnsFramesFlowShape f;
-    f.K = sh.K;
-    f.T = sh.T;
-    f.fr_two = sh.fr_two;
-    f.fr_lds_bytes = sh.fr_lds_bytes;
-    f.co_fr_two = sh.co_fr_two;
-    f.co_fr_lds_bytes = sh.co_fr_lds_bytes;
-    f.hs_two = sh.two;
-    f.hs_lds_bytes = sh.lds_bytes;
-    f.co_hs_two = sh.co_two;
-    f.co_hs_lds_bytes = sh.co_lds_bytes;
+    Phi4EnsFramesFlowShape f{phi4_ens_shape(sites, Lz), 0, 0, 0, 0};
     f.fr_stash = 1;   // the frames kernels: the row, for every K
     f.hfr_stash = 1;
-    f.hs_stash = sh.K < 8 ? 0 : 1;  // phi4_ens_heun_flow_kernel's REG
+    f.hs_stash = f.K < 8 ? 0 : 1;  // phi4_ens_heun_flow_kernel's REG
     f.mask = 0xf;  // every instance fits its registers (profiles/r07/phi4_ens_flow_frames/resources.txt)
     return f;
 }
 
 hipError_t phi4_ens_frames_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFrameArgs &f, const Phi4EnsFlowArgs &w,
                                        bool corr, bool heun, int nrep, hipStream_t s) {
-    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || f.nframes < 1 || f.loops < 1 || f.st == nullptr ||
-        f.stable == nullptr || f.dtau == nullptr || f.recs == nullptr || !ens_flow_levels_ok(w) ||
-        (a.series == nullptr && !corr) || (corr && (w.G == nullptr || w.S1 == nullptr || w.nmeas == nullptr)))
-        return hipErrorInvalidValue;
+    if (!ens_frames_ok(a, f, nrep) || !ens_flow_ok(a, w, corr)) return hipErrorInvalidValue;
     const Phi4EnsFramesFlowShape sh = phi4_ens_frames_flow_shape(a.Lx * a.Ly * a.Lz, a.Lz);
     if (!(sh.mask >> (2 * (heun ? 1 : 0) + (corr ? 1 : 0)) & 1)) return hipErrorInvalidValue;
-    const bool two2 = corr ? sh.co_fr_two : sh.fr_two;
-    const int bytes = corr ? sh.co_fr_lds_bytes : sh.fr_lds_bytes;
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsFrames, corr ? phi4_ens_corr_bytes(a.Lz) : 0);
     Phi4EnsArgs q = a;
     Phi4EnsFrameArgs fq = f;
     Phi4EnsFlowArgs wq = w;
     Phi4EnsCorrArgs cq{};
-    int two = two2 ? 1 : 0;
-    const void *fn;
-    hipError_t e;
-    if (heun) {
+    int two = l.images == 2;
+    if (heun) {  // the image count selects the instance
         void *args[] = {&q, &fq, &wq, &cq};  // the plain instances take the first three
-        fn = corr ? (two2 ? ens_heun_frames_flow_fn<true, Phi4EnsCorrArgs>(sh.K)
-                          : ens_heun_frames_flow_fn<false, Phi4EnsCorrArgs>(sh.K))
-                  : (two2 ? ens_heun_frames_flow_fn<true>(sh.K) : ens_heun_frames_flow_fn<false>(sh.K));
-        e = ens_lds_attr(fn, bytes);
-        if (e != hipSuccess) return e;
-        return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+        const void *fn = corr ? (two ? SQ_ENS_KERNEL(sh.K, phi4_ens_heun_frames_flow_kernel, true, Phi4EnsCorrArgs)
+                                     : SQ_ENS_KERNEL(sh.K, phi4_ens_heun_frames_flow_kernel, false, Phi4EnsCorrArgs))
+                              : (two ? SQ_ENS_KERNEL(sh.K, phi4_ens_heun_frames_flow_kernel, true)
+                                     : SQ_ENS_KERNEL(sh.K, phi4_ens_heun_frames_flow_kernel, false));
+        return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
     }
     void *args[] = {&q, &fq, &wq, &two, &cq};  // the plain instances take the first four
-    fn = corr ? ens_frames_flow_fn<Phi4EnsCorrArgs>(sh.K) : ens_frames_flow_fn<>(sh.K);
-    e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    const void *fn = corr ? SQ_ENS_KERNEL(sh.K, phi4_ens_frames_flow_kernel, Phi4EnsCorrArgs)
+                          : SQ_ENS_KERNEL(sh.K, phi4_ens_frames_flow_kernel);
+    return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
 }
 
 hipError_t phi4_ens_heun_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs &w, bool corr, int nrep,
                                      hipStream_t s) {
-    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < 1 || !ens_flow_levels_ok(w) ||
-        (a.series == nullptr && !corr) || (corr && (w.G == nullptr || w.S1 == nullptr || w.nmeas == nullptr)))
-        return hipErrorInvalidValue;
+    if (!ens_step_ok(a, nrep, true) || !ens_flow_ok(a, w, corr)) return hipErrorInvalidValue;
     const Phi4EnsFramesFlowShape sh = phi4_ens_frames_flow_shape(a.Lx * a.Ly * a.Lz, a.Lz);
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep, corr ? phi4_ens_corr_bytes(a.Lz) : 0);
     Phi4EnsArgs q = a;
     Phi4EnsFlowArgs wq = w;
     Phi4EnsCorrArgs cq{};
-    int two = (corr ? sh.co_hs_two : sh.hs_two) ? 1 : 0;
-    const int bytes = corr ? sh.co_hs_lds_bytes : sh.hs_lds_bytes;
+    int two = l.images == 2;
     void *args[] = {&q, &wq, &two, &cq};  // the plain instances take the first three
-    const void *fn = corr ? ens_heun_flow_fn<Phi4EnsCorrArgs>(sh.K) : ens_heun_flow_fn<>(sh.K);
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    const void *fn = corr ? SQ_ENS_KERNEL(sh.K, phi4_ens_heun_flow_kernel, Phi4EnsCorrArgs)
+                          : SQ_ENS_KERNEL(sh.K, phi4_ens_heun_flow_kernel);
+    return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
 }
 
 }  // namespace sq

@@ -153,8 +153,9 @@ int sq_phi4_ens_heun_frames_shape_info(const int dims[3], int out[4]) {
     int rc = ens_shape_dims(dims, out);
     if (rc) return rc;
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2], dims[2]);
-    out[0] = s.fr_two ? 2 : 1;
-    out[1] = s.fr_lds_bytes;
+    const sq::Phi4EnsLds fr = s.lds(sq::kPhi4EnsLdsFrames);
+    out[0] = fr.images;
+    out[1] = fr.bytes;
     out[2] = s.pc_ok ? 0xf : 0x3;  // bit m: measure = m runs on this shape; momenta need their LDS region
     out[3] = 0;
     return SQ_OK;
@@ -164,12 +165,15 @@ int sq_phi4_ens_frames_flow_shape_info(const int dims[3], int out[8]) {
     int rc = ens_shape_dims(dims, out);
     if (rc) return rc;
     const sq::Phi4EnsFramesFlowShape s = sq::phi4_ens_frames_flow_shape(dims[0] * dims[1] * dims[2], dims[2]);
-    out[0] = s.fr_two ? 2 : 1;
-    out[1] = s.fr_lds_bytes;
-    out[2] = s.co_fr_two ? 2 : 1;
-    out[3] = s.co_fr_lds_bytes;
-    out[4] = (s.hs_two ? 2 : 1) | ((s.co_hs_two ? 2 : 1) << 8);
-    out[5] = s.co_hs_lds_bytes;
+    const int sl = sq::phi4_ens_corr_bytes(dims[2]);
+    const sq::Phi4EnsLds fr = s.lds(sq::kPhi4EnsLdsFrames), cofr = s.lds(sq::kPhi4EnsLdsFrames, sl);
+    const sq::Phi4EnsLds hs = s.lds(sq::kPhi4EnsLdsStep), cohs = s.lds(sq::kPhi4EnsLdsStep, sl);  // the Heun steps
+    out[0] = fr.images;
+    out[1] = fr.bytes;
+    out[2] = cofr.images;
+    out[3] = cofr.bytes;
+    out[4] = hs.images | (cohs.images << 8);
+    out[5] = cohs.bytes;
     out[6] = s.fr_stash | (s.hfr_stash << 1) | (s.hs_stash << 2);
     out[7] = s.mask;
     return SQ_OK;

@@ -47,8 +47,7 @@
 // ascending within a quad; nothing is added in between; the wave by
 // ens_wave_sum; the waves' totals in wave order.  The guard maximum runs over
 // phi_1, every g and every phi_k.
-#define SQ_PHI4_ENS_KERNELS_ONLY
-#include "sq_phi4_ens.hip"
+#include "sq_phi4_ens_launch.h"
 #include "sq_phi4_ens_mala_dev.h"  // MalaCoef, mala_quad, mala_coef
 
 namespace sq {
@@ -200,15 +199,7 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_hmc_kernel(const Ph
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
+    const Phi4StepArgs A = ens_step_args(rc, E.clampv);
     Phi4StepArgs B = A;  // the interior steps' noise-off update at 2h
     B.h = rc.h + rc.h;
     B.sig = 0.f;
@@ -382,34 +373,24 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_hmc_kernel(const Ph
     }
 }
 
-template <typename... CA>
-const void *ens_hmc_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_hmc_kernel<1, CA...>
-           : K == 2 ? (const void *)&phi4_ens_hmc_kernel<2, CA...>
-           : K == 4 ? (const void *)&phi4_ens_hmc_kernel<4, CA...>
-                    : (const void *)&phi4_ens_hmc_kernel<8, CA...>;
-}
-
 }  // namespace
 
 hipError_t phi4_ens_hmc_launch(const Phi4EnsArgs &a, const Phi4EnsHmcArgs &w, const Phi4EnsCorrArgs *c, int nrep,
                                hipStream_t s) {
-    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < (c != nullptr ? 1 : 0) ||
-        (a.series != nullptr && a.every < 1) || w.stat == nullptr || w.nleap < 1 || w.nleap > kPhi4EnsMaxLeap)
+    if (!ens_step_ok(a, nrep, c != nullptr) || w.stat == nullptr || w.nleap < 1 || w.nleap > kPhi4EnsMaxLeap)
         return hipErrorInvalidValue;
-    if (c != nullptr && (c->G == nullptr || c->S1 == nullptr || c->nmeas == nullptr)) return hipErrorInvalidValue;
+    if (c != nullptr && !ens_corr_ok(*c)) return hipErrorInvalidValue;
     // the step launches' layouts, each by its own rule
     const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, c != nullptr ? a.Lz : 0);
-    int two = (c ? sh.co_two : sh.two) ? 1 : 0;
-    const int bytes = c ? sh.co_lds_bytes : sh.lds_bytes;
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep, c ? phi4_ens_corr_bytes(a.Lz) : 0);
+    int two = l.images == 2;
     Phi4EnsArgs q = a;
     Phi4EnsHmcArgs wq = w;
     Phi4EnsCorrArgs cq = c ? *c : Phi4EnsCorrArgs{};
     void *args[] = {&q, &wq, &two, &cq};  // the plain instances take the first three
-    const void *fn = c ? ens_hmc_fn<Phi4EnsCorrArgs>(sh.K) : ens_hmc_fn<>(sh.K);
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    const void *fn = c ? SQ_ENS_KERNEL(sh.K, phi4_ens_hmc_kernel, Phi4EnsCorrArgs)
+                       : SQ_ENS_KERNEL(sh.K, phi4_ens_hmc_kernel);
+    return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
 }
 
 }  // namespace sq

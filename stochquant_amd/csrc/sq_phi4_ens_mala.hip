@@ -60,8 +60,7 @@
 // of B) | barrier.  Three barriers per accepted step, four per rejected one.
 // A measurement point puts one more barrier in front of its own use of the
 // scratch (ens_fold), since a slow wave may still be folding the step's totals.
-#define SQ_PHI4_ENS_KERNELS_ONLY
-#include "sq_phi4_ens.hip"
+#include "sq_phi4_ens_launch.h"
 #include "sq_phi4_ens_mala_dev.h"  // MalaCoef, mala_site, mala_quad
 
 namespace sq {
@@ -153,24 +152,8 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_mala_kernel(const P
     const int r = blockIdx.x;
     const EnsGeo g = ens_geo(E);
     const Phi4EnsRec rc = E.rec[r];
-    Phi4StepArgs A{};
-    A.h = rc.h;
-    A.m2 = rc.m2;
-    A.lam6 = rc.lam6;
-    A.sig = rc.sig;
-    A.sigq = rc.sigq;
-    A.clampv = E.clampv;
-    A.k0 = rc.k0;
-    A.k1 = rc.k1;
-    MalaCoef M;
-    // block-uniform doubles, held in scalar registers (the compiler leaves the results of v_cvt / v_mul in
-    // vector ones: 14 per lane for the whole call)
-    M.h = readlane_d((double)rc.h, 0);
-    M.h4 = readlane_d(4.0 * M.h, 0);
-    M.m2 = readlane_d((double)rc.m2, 0);
-    M.lam6 = readlane_d((double)rc.lam6, 0);
-    M.km = readlane_d(3.0 + 0.5 * M.m2, 0);
-    M.l4 = readlane_d(0.25 * M.lam6, 0);
+    const Phi4StepArgs A = ens_step_args(rc, E.clampv);
+    const MalaCoef M = mala_coef(rc);
     const double sig2 = readlane_d((double)rc.sig * (double)rc.sig, 0);
     float *cur = reinterpret_cast<float *>(ens_smem);
     float *oth = two ? cur + 4 * g.Q : cur;
@@ -289,34 +272,23 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_mala_kernel(const P
     }
 }
 
-template <typename... CA>
-const void *ens_mala_fn(int K) {
-    return K == 1   ? (const void *)&phi4_ens_mala_kernel<1, CA...>
-           : K == 2 ? (const void *)&phi4_ens_mala_kernel<2, CA...>
-           : K == 4 ? (const void *)&phi4_ens_mala_kernel<4, CA...>
-                    : (const void *)&phi4_ens_mala_kernel<8, CA...>;
-}
-
 }  // namespace
 
 hipError_t phi4_ens_mala_launch(const Phi4EnsArgs &a, const Phi4EnsMalaArgs &w, const Phi4EnsCorrArgs *c, int nrep,
                                 hipStream_t s) {
-    if (!ens_shape_ok(a) || a.flags == nullptr || nrep < 1 || a.nsteps < 0 || a.every < (c != nullptr ? 1 : 0) ||
-        (a.series != nullptr && a.every < 1) || w.stat == nullptr)
-        return hipErrorInvalidValue;
-    if (c != nullptr && (c->G == nullptr || c->S1 == nullptr || c->nmeas == nullptr)) return hipErrorInvalidValue;
+    if (!ens_step_ok(a, nrep, c != nullptr) || w.stat == nullptr) return hipErrorInvalidValue;
+    if (c != nullptr && !ens_corr_ok(*c)) return hipErrorInvalidValue;
     // the step launches' layouts, each by its own rule
     const Phi4EnsShape sh = phi4_ens_shape(a.Lx * a.Ly * a.Lz, c != nullptr ? a.Lz : 0);
-    int two = (c ? sh.co_two : sh.two) ? 1 : 0;
-    const int bytes = c ? sh.co_lds_bytes : sh.lds_bytes;
+    const Phi4EnsLds l = sh.lds(kPhi4EnsLdsStep, c ? phi4_ens_corr_bytes(a.Lz) : 0);
+    int two = l.images == 2;
     Phi4EnsArgs q = a;
     Phi4EnsMalaArgs wq = w;
     Phi4EnsCorrArgs cq = c ? *c : Phi4EnsCorrArgs{};
     void *args[] = {&q, &wq, &two, &cq};  // the plain instances take the first three
-    const void *fn = c ? ens_mala_fn<Phi4EnsCorrArgs>(sh.K) : ens_mala_fn<>(sh.K);
-    hipError_t e = ens_lds_attr(fn, bytes);
-    if (e != hipSuccess) return e;
-    return hipLaunchKernel(fn, dim3((unsigned)nrep), dim3((unsigned)sh.T), args, (size_t)bytes, s);
+    const void *fn = c ? SQ_ENS_KERNEL(sh.K, phi4_ens_mala_kernel, Phi4EnsCorrArgs)
+                       : SQ_ENS_KERNEL(sh.K, phi4_ens_mala_kernel);
+    return ens_launch(fn, nrep, sh.T, l.bytes, args, s);
 }
 
 }  // namespace sq

@@ -1,9 +1,9 @@
 // sq_phi4_ens_mala_dev.h -- the device functions the Metropolis kernels share
 // (sq_phi4_ens_mala.hip, sq_phi4_ens_hmc.hip): the per-site
-// term of 2 sig^2 dH in double.  Included behind sq_phi4_ens.hip
-// (SQ_PHI4_ENS_KERNELS_ONLY); the head of sq_phi4_ens_mala.hip states the
+// term of 2 sig^2 dH in double.  The head of sq_phi4_ens_mala.hip states the
 // term and the order of summation.
 #pragma once
+#include "sq_phi4_ens_dev.h"
 
 namespace sq {
 

@@ -327,7 +327,7 @@ int sq_phi4_ens_exchange_shape_info(const int dims[3], int out[4]) {
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
     out[0] = s.K;
     out[1] = s.T;
-    out[2] = s.mom_lds_bytes;
+    out[2] = s.lds(sq::kPhi4EnsLdsStored).bytes;
     out[3] = sq::kPhi4EnsLdsBytes;
     return SQ_OK;
 }
@@ -504,7 +504,7 @@ int sq_phi4_ens_cluster_shape_info(const int dims[3], int out[4]) {
     const sq::Phi4EnsShape s = sq::phi4_ens_shape(dims[0] * dims[1] * dims[2]);
     out[0] = s.K;
     out[1] = s.T;
-    out[2] = s.mom_lds_bytes;
+    out[2] = s.lds(sq::kPhi4EnsLdsStored).bytes;
     out[3] = sq::kPhi4EnsLdsBytes;
     return SQ_OK;
 }
@@ -515,7 +515,7 @@ int sq_phi4_ensemble_cluster_improved_shape_info(const int dims[3], int out[5]) 
     const sq::Phi4EnsClusterSumShape s = sq::phi4_ens_cluster_sum_shape(dims[0] * dims[1] * dims[2]);
     out[0] = s.K;
     out[1] = s.T;
-    out[2] = s.lds_bytes;
+    out[2] = s.lds(sq::kPhi4EnsLdsStored, sq::kPhi4EnsClusterSumBytes).bytes;
     out[3] = sq::kPhi4EnsLdsBytes;
     out[4] = s.park;
     return SQ_OK;

@@ -66,9 +66,11 @@ def test_the_cluster_stream_is_declared_beside_the_exchange_stream():
         h = fh.read()
     assert re.search(r"constexpr uint32_t kPhi4EnsStreamCluster = 5;", h)
     assert h.index("kPhi4EnsStreamExchange = 4") < h.index("kPhi4EnsStreamCluster = 5")
-    with open(os.path.join(ROOT, "stochquant_amd", "csrc", "sq_phi4_ens_cluster.hip")) as fh:
+    with open(os.path.join(ROOT, "stochquant_amd", "csrc", "sq_phi4_ens_cluster_dev.h")) as fh:
         k = fh.read()
-    assert "kPhi4EnsStreamCluster << 24" in k and "#define SQ_PHI4_ENS_KERNELS_ONLY" in k
+    assert "kPhi4EnsStreamCluster << 24" in k and '#include "sq_phi4_ens_dev.h"' in k
+    with open(os.path.join(ROOT, "stochquant_amd", "csrc", "sq_phi4_ens_cluster.hip")) as fh:
+        assert '#include "sq_phi4_ens_cluster_dev.h"' in fh.read()
     import phi4_cluster_model as cm
     assert cm.STREAM_CLUSTER == 5
 
@@ -76,7 +78,10 @@ def test_the_cluster_stream_is_declared_beside_the_exchange_stream():
 def test_the_source_is_in_the_build_list():
     from stochquant_amd import build
     assert "sq_phi4_ens_cluster.hip" in build.DEVICE_SOURCES
-    assert build.INCLUDES["sq_phi4_ens_cluster.hip"] == build.INCLUDES["sq_phi4_ens_exchange.hip"]
+    # the kernel's own file, then exactly what the exchange unit depends on
+    assert build.INCLUDES["sq_phi4_ens_cluster.hip"] == \
+        ["sq_phi4_ens_cluster_dev.h"] + build.INCLUDES["sq_phi4_ens_exchange.hip"]
+    assert "sq_phi4_ens_cluster_dev.h" not in build.INCLUDES["sq_phi4_ens_exchange.hip"]
 
 
 def test_null_handle_is_an_argument_error(sqlib):

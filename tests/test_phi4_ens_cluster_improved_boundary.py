@@ -57,11 +57,14 @@ def test_header_carries_the_definition():
 def test_the_source_is_in_the_build_list():
     from stochquant_amd import build
     assert "sq_phi4_ens_cluster_improved.hip" in build.DEVICE_SOURCES
-    assert build.INCLUDES["sq_phi4_ens_cluster_improved.hip"] == \
-        ["sq_phi4_ens_cluster.hip"] + build.INCLUDES["sq_phi4_ens_cluster.hip"]
+    # the cluster kernel's file and everything the cluster unit depends on: the two units' lists are one
+    assert build.INCLUDES["sq_phi4_ens_cluster_improved.hip"] == build.INCLUDES["sq_phi4_ens_cluster.hip"]
+    assert build.INCLUDES["sq_phi4_ens_cluster_improved.hip"][0] == "sq_phi4_ens_cluster_dev.h"
     with open(os.path.join(ROOT, "stochquant_amd", "csrc", "sq_phi4_ens_cluster_improved.hip")) as fh:
         k = fh.read()
-    assert '#include "sq_phi4_ens_cluster.hip"' in k and "#define SQ_PHI4_ENS_CLUSTER_KERNEL_ONLY" in k
+    assert '#include "sq_phi4_ens_cluster_dev.h"' in k and "KERNEL_ONLY" not in k
+    with open(os.path.join(ROOT, "stochquant_amd", "csrc", "sq_phi4_ens_cluster_dev.h")) as fh:
+        assert "phi4_ens_cluster_kernel(" in fh.read()
 
 
 def test_null_handle_and_arguments_come_before_any_device_work(sqlib):

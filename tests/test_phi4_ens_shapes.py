@@ -190,3 +190,125 @@ def test_sampler_measure_list_covers_every_class(infos):
     missing = {measure_class(s, infos[s]) for s in SAMPLER_MEASURE_SHAPES
                if infos[s]["K"] * infos[s]["T"] > s[0] * s[1] * s[2] // 4}
     assert missing == {(2, 2, 2), (4, 2, 2), (8, 2, 1), (8, 1, 1)}, missing
+
+
+# ---- the one LDS rule (sq_phi4_ens.h, phi4_ens_lds), stated here and held against every number that every
+# *_shape_info entry point returns, for every legal shape.  A launch's dynamic LDS is the image(s) of the lattice
+# (4 bytes a site), the launch's scratch, then the bytes its measurement keeps behind the scratch; two images
+# exactly when 2 * 4 * sites + scratch + behind fits in 160 KiB, and always one for a launch that works on the
+# stored field.
+
+def lds_rule(sites, kind, behind):
+    """(images, bytes) of a launch of `kind`: "step", "frames" or "stored"."""
+    rest = (FRAME_SCRATCH if kind == "frames" else SCRATCH) + behind
+    images = 2 if kind != "stored" and 2 * 4 * sites + rest <= LDS_LIMIT else 1
+    return images, images * 4 * sites + rest
+
+
+def none(Lz):
+    return 0
+
+
+def corr(Lz):  # the slice sums: Lz doubles
+    return 8 * Lz
+
+
+def pcorr(Lz):  # the projections: 2 Lz doubles
+    return 16 * Lz
+
+
+def sums(Lz):  # the cluster sums' per-weight totals
+    return 32
+
+
+def momenta_fit(sites, Lz):
+    """One image fits in each of the three launches that take momenta."""
+    return all(4 * sites + scratch + pcorr(Lz) <= LDS_LIMIT for scratch in (SCRATCH, FRAME_SCRATCH, SCRATCH))
+
+
+# (entry point; index into its out[], or (index, shift) of a byte packed into it; launch kind; bytes behind the
+# scratch; which of the rule's two numbers)
+LDS_TABLE = [
+    ("sq_phi4_ens_shape_info", 2, "step", none, "images"),
+    ("sq_phi4_ens_shape_info", 3, "step", none, "bytes"),
+    ("sq_phi4_ens_shape_info", 4, "frames", none, "images"),
+    ("sq_phi4_ens_shape_info", 5, "frames", none, "bytes"),
+    ("sq_phi4_ens_shape_info", 6, "stored", none, "bytes"),                  # moments
+    ("sq_phi4_ens_corr_shape_info", 0, "step", corr, "images"),
+    ("sq_phi4_ens_corr_shape_info", 1, "step", corr, "bytes"),
+    ("sq_phi4_ens_corr_shape_info", 2, "frames", corr, "images"),
+    ("sq_phi4_ens_corr_shape_info", 3, "frames", corr, "bytes"),
+    ("sq_phi4_ens_corr_shape_info", 4, "stored", corr, "bytes"),             # slices
+    ("sq_phi4_ens_pcorr_shape_info", 0, "step", pcorr, "images"),
+    ("sq_phi4_ens_pcorr_shape_info", 1, "step", pcorr, "bytes"),
+    ("sq_phi4_ens_pcorr_shape_info", 2, "frames", pcorr, "images"),
+    ("sq_phi4_ens_pcorr_shape_info", 3, "frames", pcorr, "bytes"),
+    ("sq_phi4_ens_pcorr_shape_info", 4, "stored", pcorr, "bytes"),           # pslices
+    ("sq_phi4_ens_flow_shape_info", 0, "step", none, "images"),
+    ("sq_phi4_ens_flow_shape_info", 1, "step", none, "bytes"),
+    ("sq_phi4_ens_flow_shape_info", 2, "step", corr, "images"),
+    ("sq_phi4_ens_flow_shape_info", 3, "step", corr, "bytes"),
+    ("sq_phi4_ens_flow_shape_info", 4, "step", corr, "bytes"),               # flowed: it ping-pongs as a step launch
+    ("sq_phi4_ens_frames_flow_shape_info", 0, "frames", none, "images"),
+    ("sq_phi4_ens_frames_flow_shape_info", 1, "frames", none, "bytes"),
+    ("sq_phi4_ens_frames_flow_shape_info", 2, "frames", corr, "images"),
+    ("sq_phi4_ens_frames_flow_shape_info", 3, "frames", corr, "bytes"),
+    ("sq_phi4_ens_frames_flow_shape_info", (4, 0), "step", none, "images"),  # the Heun step launch
+    ("sq_phi4_ens_frames_flow_shape_info", (4, 8), "step", corr, "images"),
+    ("sq_phi4_ens_frames_flow_shape_info", 5, "step", corr, "bytes"),
+    ("sq_phi4_ens_heun_frames_shape_info", 0, "frames", none, "images"),
+    ("sq_phi4_ens_heun_frames_shape_info", 1, "frames", none, "bytes"),
+    ("sq_phi4_ens_exchange_shape_info", 2, "stored", none, "bytes"),
+    ("sq_phi4_ens_cluster_shape_info", 2, "stored", none, "bytes"),
+    ("sq_phi4_ensemble_cluster_improved_shape_info", 2, "stored", sums, "bytes"),
+]
+LDS_CALLS = sorted({row[0] for row in LDS_TABLE})
+
+
+def test_the_lds_table_names_every_shape_info_entry_point():
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "include", "stochquant.h")) as fh:
+        declared = set(re.findall(r"\bint\s+(sq_phi4_ens\w*shape_info)\s*\(", fh.read()))
+    assert declared == set(LDS_CALLS)
+
+
+def test_the_legal_shapes_lie_on_both_sides_of_every_threshold_of_the_rule():
+    seen, fits = {}, set()
+    for Lx, Ly, Lz in legal_shapes():
+        sites = Lx * Ly * Lz
+        fits.add(momenta_fit(sites, Lz))
+        for _, _, kind, behind, _ in LDS_TABLE:
+            seen.setdefault((kind, behind.__name__), set()).add(lds_rule(sites, kind, behind(Lz))[0])
+    for (kind, _), images in seen.items():
+        assert images == ({1} if kind == "stored" else {1, 2})
+    assert fits == {True, False}
+
+
+def test_every_shape_info_number_follows_the_one_rule(sqlib):
+    import ctypes
+    dims = (ctypes.c_int * 3)()
+    out = (ctypes.c_int * 8)()
+    fns = {name: getattr(sqlib, name) for name in LDS_CALLS}
+    rows = {name: [r for r in LDS_TABLE if r[0] == name] for name in LDS_CALLS}
+    nshapes = 0
+    for Lx, Ly, Lz in legal_shapes():
+        sites = Lx * Ly * Lz
+        dims[0], dims[1], dims[2] = Lx, Ly, Lz
+        nshapes += 1
+        fit = momenta_fit(sites, Lz)
+        for name in LDS_CALLS:
+            rc = fns[name](dims, out)
+            if name == "sq_phi4_ens_pcorr_shape_info" and not fit:
+                assert rc == -1, (name, Lx, Ly, Lz)  # SQ_E_ARG: the shape cannot hold momenta
+                continue
+            assert rc == 0, (name, Lx, Ly, Lz)
+            for _, idx, kind, behind, which in rows[name]:
+                images, nbytes = lds_rule(sites, kind, behind(Lz))
+                got = out[idx] if isinstance(idx, int) else (out[idx[0]] >> idx[1]) & 0xff
+                assert got == (images if which == "images" else nbytes), (name, idx, Lx, Ly, Lz)
+                assert nbytes <= LDS_LIMIT, (name, idx, Lx, Ly, Lz)
+            if name == "sq_phi4_ens_heun_frames_shape_info":
+                assert out[2] == (0xf if fit else 0x3), (Lx, Ly, Lz)  # momenta only where they fit
+    assert nshapes == 45843
