@@ -1009,6 +1009,116 @@ int sq_phi4_ensemble_step_hmc_cluster_improved(sq_phi4_ens *e, int nrounds, int 
                                           long long *weights /*[nrounds][R][sites][7], nullable*/);
 int sq_phi4_ensemble_cluster_improved_shape_info(const int dims[3], int out[5] /*K, T, LDS bytes, LDS limit, park*/);
 
+/* Checkpoints of the phi^4 ensemble, and the field digest they rest on
+ * (DESIGN.md §4.3).  ABI 6: symbols added, none changed; named
+ * sq_phi4_ensemble_* as the cluster sums' calls are.  The contract: a run that
+ * saves, ends and resumes in a new process returns the bits of the run that
+ * never stopped.
+ *
+ * The field digest.  With
+ *   mix(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;
+ *            x *= 0x94D049BB133111EB;  x ^= x >> 31          (uint64, wrapping)
+ * replica r's digest is
+ *   D_r = sum over sites i = 0 .. sites-1 of mix((uint64(i) << 32) | bits32(phi_r[i]))   mod 2^64,
+ * i the site's index in the replica's row (z slowest, sq_phi4_ens_download's
+ * order) and bits32 the float's IEEE pattern: -0.0, every NaN payload and the
+ * infinities are told apart.  A wrapping integer sum is exact in any order, so
+ * the kernel (sq_phi4_ens_digest.hip: one work-group per replica, 16-byte
+ * loads, a wave reduction, LDS across waves, one 8-byte store) and the host
+ * agree bit for bit.  digest(bytes), used below, is the same sum over a byte
+ * string read as little-endian 32-bit words, the last one zero-padded.
+ * sq_phi4_ensemble_digest: out[r] = D of replica first + r, r < count; it
+ * reads the fields and changes nothing.
+ *
+ * A checkpoint named <path> is three little-endian files:
+ *   <path>        NumPy .npy v1.0: the magic "\x93NUMPY", bytes 1 and 0, the
+ *                 header's length as uint16, the header
+ *                 "{'descr': '<f4', 'fortran_order': False, 'shape': (R, Lz, Ly, Lx), }"
+ *                 padded with spaces so that the data starts on a multiple of
+ *                 64 bytes, its last byte '\n'; then R Lz Ly Lx float32 in C
+ *                 order.  np.load(path) is sq_phi4_ens_download's array.  A
+ *                 reader accepts exactly this header.
+ *   <path>.state  the per-replica tables ("sections"), raw, each starting on
+ *                 an 8-byte boundary, zero bytes between them and up to the
+ *                 file's end, which is a multiple of 8.
+ *   <path>.json   one JSON object with exactly these keys, no byte behind its
+ *                 closing brace:
+ *     "format": "stochquant-phi4-ensemble", "version": 1,
+ *     "dims": [Lx, Ly, Lz], "R", "loops", "adapt_dtau" (0 or 1),
+ *     "clamp_bits": the double's IEEE pattern as an unsigned decimal,
+ *     "exchange_round", "cluster_sweep": unsigned 64-bit decimals,
+ *     "ladder": slots per ladder, 0 none,
+ *     "momenta": [[nx, ny], ...], "flow_levels": [n_1, ...],
+ *     "flow_eps_bits", "flow_m2_bits", "flow_lambda_bits": patterns (a NaN m2
+ *       or lambda means "the replica's own"),
+ *     "clamp", "flow_eps", "flow_m2", "flow_lambda": decimal copies, null
+ *       when not finite; informative only, never read,
+ *     "field_digest": [D_0, ..., D_{R-1}],
+ *     "field_bytes", "state_bytes": the sizes of the other two files,
+ *     "state_digest": digest(<path>.state),
+ *     "meta_digest": digest of the little-endian bytes of the uint64 words
+ *       version, Lx, Ly, Lz, R, loops, clamp_bits, adapt_dtau, exchange_round,
+ *       cluster_sweep, ladder, M, nx_1, ny_1, ..., F, n_1, ..., flow_eps_bits,
+ *       flow_m2_bits, flow_lambda_bits, field_bytes, state_bytes, state_digest,
+ *       D_0 .. D_{R-1}, the number of sections, every section's offset in the
+ *       table's order (negative values as two's complement),
+ *     "sections": [{"name", "dtype", "shape", "offset"}, ...].
+ *   Integers are JSON integers (no fraction, no exponent); strings are plain
+ *   ASCII without escapes; a key appears once.
+ *
+ * The sections, with nt = Lz / 2 + 1, M momenta, F flow levels (dtype, shape):
+ *   seed, step                      <u8 [R]
+ *   dtau, m2, lambda, C             <f8 [R]
+ *   flags                           <i4 [R]       the guard flags
+ *   frame_dtau, frame_C             <f8 [R]       the frame state ...
+ *   frame_T, frame_V                <f4 [R]
+ *   frame_init, frame_cnt, frame_fired, frame_flag, frame_exec   <i4 [R]
+ *   frame_records                   <f4 [R][3][loops]   M | D | A of the last frame; optional: there
+ *                                                 once a frames call has run
+ *   corr_G <f8 [R][nt], corr_S1 <f8 [R], corr_nmeas <i8 [R]
+ *   pcorr_G <f8 [R][M][nt]          exactly when M > 0
+ *   pcorr_nmeas                     <i8 [R]
+ *   flow_G <f8 [R][F][nt], flow_S1 <f8 [R][F], flow_nmeas <i8 [R][F]   exactly when F > 0
+ *   mala_stats <i8 [R][3], hmc_stats <i8 [R][4]   optional: there once the sampler has run
+ *   exchange_stats <i8 [R][2], walkers <i4 [R], cluster_stats <i8 [R][5]
+ * A table that was never allocated reads as zeros; it is written as an absent
+ * section and reads as zeros after the load.  Any other name is refused.
+ *
+ * Not saved, by decision: the records of the last call that the handle merely
+ * holds for its caller (series, MALA / HMC / exchange / cluster records, bond
+ * and label dumps, cluster weights); scratch and derived tables (twiddles,
+ * parked labels, the *_tmp buffers, the device records, which are rebuilt from
+ * the parameters); and sq_phi4_ens_perf, which restarts at zero.
+ *
+ * sq_phi4_ensemble_save synchronises the stream, reads and writes; the handle
+ * goes on bit for bit as one that never saved.  Each file is written under a
+ * temporary name in the same directory (<file>.tmp.<pid>.<count>, never shared
+ * by two calls), flushed to the disk and renamed into place, and the directory
+ * is flushed; the .json last; no temporary is left behind.  A torn set (files
+ * of two saves, as two handles saving to one path at one time can leave) is
+ * detected by the sizes and digests and refused, not repaired.
+ *
+ * sq_phi4_ensemble_load, fields_only == 0: dims, R, loops, clamp and
+ * adapt_dtau must be the handle's (SQ_E_ARG naming the first that is not).
+ * Everything is validated before the handle is touched: the JSON complete and
+ * strict, the version, the section table (names, dtypes, shapes, offsets
+ * inside the file and not overlapping), the sizes, the .npy header, the
+ * host-recomputed digests, every replica's parameters by
+ * sq_phi4_ens_create's bound, momenta, flow levels and ladder by the setters'
+ * own rules.  A refused load (SQ_E_ARG) changes nothing.  After the upload the
+ * digest kernel runs on the device copy; a mismatch is SQ_E_HIP.  Seeds come
+ * from the file.  fields_only != 0: only dims and R must match; only the field
+ * rows are uploaded (and digest-checked), nothing else changes.
+ *
+ * sq_phi4_ensemble_checkpoint_info needs no device and no handle: info =
+ * {version, Lx, Ly, Lz, R, loops, adapt_dtau, number of sections}, *clamp
+ * (nullable) the clamp.  verify != 0 also opens the other two files and runs
+ * every check of the load that needs no handle. */
+int sq_phi4_ensemble_digest(sq_phi4_ens *e, int first, int count, unsigned long long *out /*[count]*/);
+int sq_phi4_ensemble_save(sq_phi4_ens *e, const char *path);
+int sq_phi4_ensemble_load(sq_phi4_ens *e, const char *path, int fields_only);
+int sq_phi4_ensemble_checkpoint_info(const char *path, int verify, long long info[8], double *clamp /*nullable*/);
+
 /* Gradient-flow measurements of the phi^4 ensemble: the sums and the
  * time-slice correlator taken of a smoothed copy of a replica's field, inside
  * the resident kernel.  ABI 6: symbols added, none changed.

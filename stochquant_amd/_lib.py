@@ -256,6 +256,11 @@ SIGNATURES = {
                                                              ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int),
                                                              _D, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ensemble_cluster_improved_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ensemble_digest": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _UL]),
+    "sq_phi4_ensemble_save": (ctypes.c_int, [_P, ctypes.c_char_p]),
+    "sq_phi4_ensemble_load": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.c_int]),
+    "sq_phi4_ensemble_checkpoint_info": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong),
+                                                       _D]),
 }
 SQ_PHI4_ENS_MAX_MOMENTA = 8
 SQ_PHI4_ENS_MAX_FLOW_LEVELS = 4

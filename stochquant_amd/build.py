@@ -30,13 +30,13 @@ ARCH = os.environ.get("SQ_OFFLOAD_ARCH", "gfx950")
 
 DEVICE_SOURCES = ["sq_phi4.hip", "sq_phi4_run.hip", "sq_qm1d.hip", "sq_qm1d_ens.hip", "sq_qm1d_gs.hip", "sq_phi4_ens.hip",
                   "sq_phi4_ens_flow.hip", "sq_phi4_ens_flow_frames.hip", "sq_phi4_ens_mala.hip", "sq_phi4_ens_hmc.hip", "sq_phi4_ens_exchange.hip", "sq_phi4_ens_cluster.hip",
-                  "sq_phi4_ens_cluster_improved.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
+                  "sq_phi4_ens_cluster_improved.hip", "sq_phi4_ens_digest.hip", "sq_selftest.hip", "sq_p2p.hip", "sq_fields.hip"]
 HOST_SOURCES = ["sq_core.cpp", "sq_comm.cpp", "sq_phi4_create.cpp", "sq_phi4_plan.cpp", "sq_phi4_steps.cpp",
                 "sq_phi4_frames.cpp", "sq_phi4_fields.cpp", "sq_qm1d_host.cpp", "sq_ens.cpp", "sq_phi4_ens.cpp",
                 "sq_phi4_ens_frames.cpp", "sq_phi4_ens_corr.cpp", "sq_phi4_ens_flow.cpp", "sq_phi4_ens_samplers.cpp",
-                "sq_diag.cpp", "sq_io.cpp"]
+                "sq_phi4_ens_ckpt_format.cpp", "sq_phi4_ens_ckpt.cpp", "sq_diag.cpp", "sq_io.cpp"]
 HEADERS = ["sq_internal.h", "sq_ctx.h", "sq_buf.h", "sq_phi4_ens_host.h", "sq_rng.h", "sq_noise_consts.h", "sq_dpp.h", "sq_glibcf.h", "sq_ens.h", "sq_phi4_ens.h",
-           "sq_qm1d_math.h"]
+           "sq_qm1d_math.h", "sq_json.h", "sq_phi4_ens_ckpt_format.h"]
 # per device source, the project's device files it includes, directly or through one of them: other device
 # sources, the *_dev.h device headers and the ensemble's launch header (tests/test_build_table.py scans the
 # sources and holds this table to them)

@@ -17,8 +17,16 @@
 
 #include "../../include/stochquant.h"
 #include "sq_internal.h"
+#include "sq_json.h"
 
 namespace {
+
+// the metadata is read with the key scanners of sq_json.h
+using sq::json::json_dbl;
+using sq::json::json_dims;
+using sq::json::json_int;
+using sq::json::json_uint;
+using sq::json::read_text;
 
 int io_fail(const std::string &m) { return sq::set_error(SQ_E_ARG, m); }
 
@@ -83,46 +91,6 @@ bool read_npy(const char *path, std::vector<float> &out, const long long want[3]
     }
     fclose(fp);
     return ok;
-}
-
-bool read_text(const std::string &path, std::string *j) {
-    FILE *fp = fopen(path.c_str(), "r");
-    if (!fp) return false;
-    char buf[512];
-    size_t n;
-    while ((n = fread(buf, 1, sizeof buf, fp)) > 0 && j->size() < (1u << 16)) j->append(buf, n);
-    fclose(fp);
-    return true;
-}
-
-bool json_dims(const std::string &j, long long d[3]) {
-    const size_t p = j.find("\"dims\":");
-    if (p == std::string::npos) return false;
-    const size_t b = j.find('[', p);
-    return b != std::string::npos && sscanf(j.c_str() + b + 1, "%lld , %lld , %lld", &d[0], &d[1], &d[2]) == 3;
-}
-
-long long json_int(const std::string &j, const char *key, bool *found) {
-    const std::string k = std::string("\"") + key + "\":";
-    const size_t p = j.find(k);
-    *found = p != std::string::npos;
-    return *found ? strtoll(j.c_str() + p + k.size(), nullptr, 10) : 0;
-}
-
-// Unsigned 64-bit fields (seed, step): strtoull, so values >= 2^63 round-trip
-// (strtoll would saturate them to LLONG_MAX).
-unsigned long long json_uint(const std::string &j, const char *key, bool *found) {
-    const std::string k = std::string("\"") + key + "\":";
-    const size_t p = j.find(k);
-    *found = p != std::string::npos;
-    return *found ? strtoull(j.c_str() + p + k.size(), nullptr, 10) : 0ull;
-}
-
-double json_dbl(const std::string &j, const char *key, bool *found) {
-    const std::string k = std::string("\"") + key + "\":";
-    const size_t p = j.find(k);
-    *found = p != std::string::npos;
-    return *found ? strtod(j.c_str() + p + k.size(), nullptr) : 0.0;
 }
 
 }  // namespace

@@ -7,18 +7,16 @@
 // uses (sq_phi4_ens_host.h).
 #include "sq_phi4_ens_host.h"
 
+#include "sq_phi4_ens_ckpt_format.h"
+
 using namespace sq;
 
 namespace {
 
-// What is wrong with a lattice shape, nullptr for a legal one (sq_phi4_ens_create, the *_shape_info).
-const char *ens_dims_error(long long Lx, long long Ly, long long Lz) {
-    if (Lx != 8 && Lx != 16 && Lx != 32 && Lx != 64) return "a phi^4 ensemble needs Lx in {8, 16, 32, 64}";
-    if (Ly < 2 || Lz < 2) return "a phi^4 ensemble needs Ly >= 2 and Lz >= 2";
-    if (Ly > sq::kPhi4EnsMaxSites || Lz > sq::kPhi4EnsMaxSites || Lx * Ly * Lz > sq::kPhi4EnsMaxSites)
-        return "a phi^4 ensemble needs Lx Ly Lz <= 32768 sites (one LDS image per lattice)";
-    return nullptr;
-}
+// What is wrong with a lattice shape, nullptr for a legal one (sq_phi4_ens_create, the *_shape_info): the rule a
+// checkpoint's reader applies as well.
+static_assert(sq::ckpt::kMaxSites == sq::kPhi4EnsMaxSites, "one site limit");
+const char *ens_dims_error(long long Lx, long long Ly, long long Lz) { return sq::ckpt::dims_error(Lx, Ly, Lz); }
 
 }  // namespace
 

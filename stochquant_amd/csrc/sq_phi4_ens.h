@@ -266,6 +266,11 @@ hipError_t phi4_ens_heun_flow_launch(const Phi4EnsArgs &a, const Phi4EnsFlowArgs
 
 // out[5 r ..] = S1, S2, S4, NN, max |phi| of replica first + r's field, r < count.
 hipError_t phi4_ens_moments_launch(const Phi4EnsArgs &a, int first, int count, double *out, hipStream_t s);
+// out[r] = the 64-bit digest of replica first + r's field, r < count (sq_phi4_ens_digest.hip; include/stochquant.h
+// has the definition): field [nrep][sites] and out in device memory, one work-group per replica, nothing written
+// but out.  The caller checks the range against its nrep.
+hipError_t phi4_ens_digest_launch(const float *field, int sites, int first, int count, unsigned long long *out,
+                                  hipStream_t s);
 // phi = amp * Philox normal(replica's key, stream 2, site): phi4_init_kernel's field per replica.
 hipError_t phi4_ens_init_launch(const Phi4EnsArgs &a, int nrep, float amp, hipStream_t s);
 

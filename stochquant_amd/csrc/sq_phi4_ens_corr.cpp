@@ -2,9 +2,41 @@
 // statistics every *correlator call shares.
 #include "sq_phi4_ens_host.h"
 
+#include "sq_phi4_ens_ckpt_format.h"
+
 using namespace sq;
 
 namespace sq {
+
+const char *ens_momenta_shape_error(int sites, int Lz) {
+    return sq::phi4_ens_shape(sites, Lz).pc_ok
+               ? nullptr
+               : "the lattice shape leaves no LDS for the momentum projections (16 Lz bytes)";
+}
+
+int ens_apply_momenta(sq_phi4_ens *e, int M, const int *nxy) {
+    DeviceGuard g(e->dev);
+    const size_t Lx = (size_t)e->Lx, Ly = (size_t)e->Ly, R = (size_t)e->R, nt = (size_t)e->nt;
+    const size_t nx = SQ_PHI4_ENS_MAX_MOMENTA * Lx, ny = SQ_PHI4_ENS_MAX_MOMENTA * Ly;
+    int rc = ens_reserve(e->ptab, 2 * (nx + ny));
+    if (!rc) rc = ens_reserve(e->pG, R * (size_t)M * nt);
+    if (rc) return rc;
+    std::vector<double> tab(2 * (nx + ny), 0.0);
+    for (int m = 0; m < M; ++m) {
+        rc = sq_phi4_ens_momentum_table(e->Lx, nxy[2 * m], &tab[(size_t)m * Lx], &tab[nx + (size_t)m * Lx]);
+        if (!rc)
+            rc = sq_phi4_ens_momentum_table(e->Ly, nxy[2 * m + 1], &tab[2 * nx + (size_t)m * Ly],
+                                            &tab[2 * nx + ny + (size_t)m * Ly]);
+        if (rc) return rc;
+    }
+    SQ_HIP(hipMemcpy(e->ptab.data(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    e->pM = M;  // the accumulators' layout is [R][M][nt] from here on: all of them start over
+    for (int i = 0; i < 2 * M; ++i) e->pn[i] = nxy[i];
+    if (M > 0) SQ_HIP(hipMemsetAsync(e->pG.data(), 0, sizeof(double) * R * (size_t)M * nt, e->stream));
+    SQ_HIP(hipMemsetAsync(e->pN.data(), 0, sizeof(long long) * R, e->stream));
+    SQ_HIP(hipStreamSynchronize(e->stream));
+    return SQ_OK;
+}
 
 Phi4EnsCorrArgs ens_corr_args(const sq_phi4_ens *e) {
     sq::Phi4EnsCorrArgs c{};
@@ -144,34 +176,9 @@ int sq_phi4_ens_momentum_table(int L, int n, double *c, double *s) {
 
 int sq_phi4_ens_set_momenta(sq_phi4_ens *e, int M, const int *nxy) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
-    if (M < 0 || M > SQ_PHI4_ENS_MAX_MOMENTA) return fail(SQ_E_ARG, "0 <= M <= SQ_PHI4_ENS_MAX_MOMENTA momenta");
-    if (M > 0 && !nxy) return fail(SQ_E_ARG, "null argument");
-    for (int m = 0; m < M; ++m)
-        if (nxy[2 * m] < 0 || nxy[2 * m] >= e->Lx || nxy[2 * m + 1] < 0 || nxy[2 * m + 1] >= e->Ly)
-            return fail(SQ_E_ARG, "a momentum needs 0 <= nx < Lx and 0 <= ny < Ly");
-    if (!sq::phi4_ens_shape((int)e->sites, e->Lz).pc_ok)
-        return fail(SQ_E_ARG, "the lattice shape leaves no LDS for the momentum projections (16 Lz bytes)");
-    DeviceGuard g(e->dev);
-    const size_t Lx = (size_t)e->Lx, Ly = (size_t)e->Ly, R = (size_t)e->R, nt = (size_t)e->nt;
-    const size_t nx = SQ_PHI4_ENS_MAX_MOMENTA * Lx, ny = SQ_PHI4_ENS_MAX_MOMENTA * Ly;
-    int rc = ens_reserve(e->ptab, 2 * (nx + ny));
-    if (!rc) rc = ens_reserve(e->pG, R * (size_t)M * nt);
-    if (rc) return rc;
-    std::vector<double> tab(2 * (nx + ny), 0.0);
-    for (int m = 0; m < M; ++m) {
-        rc = sq_phi4_ens_momentum_table(e->Lx, nxy[2 * m], &tab[(size_t)m * Lx], &tab[nx + (size_t)m * Lx]);
-        if (!rc)
-            rc = sq_phi4_ens_momentum_table(e->Ly, nxy[2 * m + 1], &tab[2 * nx + (size_t)m * Ly],
-                                            &tab[2 * nx + ny + (size_t)m * Ly]);
-        if (rc) return rc;
-    }
-    SQ_HIP(hipMemcpy(e->ptab.data(), tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    e->pM = M;  // the accumulators' layout is [R][M][nt] from here on: all of them start over
-    for (int i = 0; i < 2 * M; ++i) e->pn[i] = nxy[i];
-    if (M > 0) SQ_HIP(hipMemsetAsync(e->pG.data(), 0, sizeof(double) * R * (size_t)M * nt, e->stream));
-    SQ_HIP(hipMemsetAsync(e->pN.data(), 0, sizeof(long long) * R, e->stream));
-    SQ_HIP(hipStreamSynchronize(e->stream));
-    return SQ_OK;
+    if (const char *why = sq::ckpt::momenta_error(e->Lx, e->Ly, M, nxy)) return fail(SQ_E_ARG, why);
+    if (const char *why = ens_momenta_shape_error((int)e->sites, e->Lz)) return fail(SQ_E_ARG, why);
+    return ens_apply_momenta(e, M, nxy);
 }
 
 int sq_phi4_ens_get_momenta(sq_phi4_ens *e, int *M, int *nxy) {

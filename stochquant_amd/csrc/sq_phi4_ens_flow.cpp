@@ -2,6 +2,8 @@
 // frames is sq_phi4_ens_run_frames_flow (sq_phi4_ens_frames.cpp).
 #include "sq_phi4_ens_host.h"
 
+#include "sq_phi4_ens_ckpt_format.h"
+
 using namespace sq;
 
 namespace {
@@ -72,28 +74,10 @@ int ens_sync_flow(sq_phi4_ens *e) {
     return SQ_OK;
 }
 
-}  // namespace sq
-
-extern "C" {
-
-int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels, const double *m2,
-                         const double *lambda) {
-    if (!e) return fail(SQ_E_ARG, "null ensemble");
-    if (nlevels < 0 || nlevels > SQ_PHI4_ENS_MAX_FLOW_LEVELS)
-        return fail(SQ_E_ARG, "0 <= nlevels <= SQ_PHI4_ENS_MAX_FLOW_LEVELS flow levels");
+int ens_apply_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels, double fm2, double flam) {
     DeviceGuard g(e->dev);
     const size_t R = (size_t)e->R, nt = (size_t)e->nt, F = (size_t)nlevels;
     if (nlevels > 0) {
-        if (!levels) return fail(SQ_E_ARG, "null argument");
-        for (int l = 0; l < nlevels; ++l)
-            if (levels[l] < (l ? levels[l - 1] + 1 : 0) || levels[l] > SQ_PHI4_ENS_MAX_FLOW_STEPS)
-                return fail(SQ_E_ARG, "flow levels must ascend strictly within [0, SQ_PHI4_ENS_MAX_FLOW_STEPS]");
-        const double fm2 = m2 ? *m2 : NAN, flam = lambda ? *lambda : NAN;
-        if ((m2 && !std::isfinite(fm2)) || (lambda && !std::isfinite(flam)))
-            return fail(SQ_E_ARG, "the flow's m2 and lambda must be finite");
-        for (const auto &r : e->rep)  // every replica's flow coefficients or none
-            if (!ens_params_ok(e->p.clamp, eps, m2 ? fm2 : r.m2, lambda ? flam : r.lambda, 0.0))
-                return fail(SQ_E_ARG, "flow parameters must be finite with eps > 0 and eps * drift(clamp) < 1e30");
         if (R * F * nt > e->fG.cap()) {  // all three or none: a failure leaves the handle as it was
             DevBuf<double> G, S1;
             DevBuf<long long> N;
@@ -117,6 +101,27 @@ int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *lev
         SQ_HIP(hipStreamSynchronize(e->stream));
     }
     return SQ_OK;
+}
+
+}  // namespace sq
+
+extern "C" {
+
+int sq_phi4_ens_set_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels, const double *m2,
+                         const double *lambda) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nlevels < 0 || nlevels > SQ_PHI4_ENS_MAX_FLOW_LEVELS)
+        return fail(SQ_E_ARG, sq::ckpt::flow_levels_error(nlevels, nullptr));
+    const double fm2 = m2 ? *m2 : NAN, flam = lambda ? *lambda : NAN;
+    if (nlevels > 0) {
+        if (const char *why = sq::ckpt::flow_levels_error(nlevels, levels)) return fail(SQ_E_ARG, why);
+        if ((m2 && !std::isfinite(fm2)) || (lambda && !std::isfinite(flam)))
+            return fail(SQ_E_ARG, "the flow's m2 and lambda must be finite");
+        for (const auto &r : e->rep)  // every replica's flow coefficients or none
+            if (!ens_params_ok(e->p.clamp, eps, m2 ? fm2 : r.m2, lambda ? flam : r.lambda, 0.0))
+                return fail(SQ_E_ARG, "flow parameters must be finite with eps > 0 and eps * drift(clamp) < 1e30");
+    }
+    return ens_apply_flow(e, eps, nlevels, levels, fm2, flam);
 }
 
 int sq_phi4_ens_get_flow(sq_phi4_ens *e, double *eps, int *nlevels, int *levels, double *m2, double *lambda) {

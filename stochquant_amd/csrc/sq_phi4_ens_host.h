@@ -1,7 +1,7 @@
 // sq_phi4_ens_host.h -- the phi^4 lattice ensemble's handle and the helpers its host files share:
 // sq_phi4_ens.cpp (the handle, parameters, Euler and Heun steps), sq_phi4_ens_frames.cpp,
-// sq_phi4_ens_corr.cpp (correlator, momenta), sq_phi4_ens_flow.cpp and sq_phi4_ens_samplers.cpp (MALA, HMC,
-// exchange, cluster).  Host only; the kernels' side is sq_phi4_ens.h.
+// sq_phi4_ens_corr.cpp (correlator, momenta), sq_phi4_ens_flow.cpp, sq_phi4_ens_samplers.cpp (MALA, HMC,
+// exchange, cluster) and sq_phi4_ens_ckpt.cpp (digest, save, load).  Host only; the kernels' side is sq_phi4_ens.h.
 //
 // Every buffer of the handle is a Buf: it grows with reserve() and the handle's destructor frees it.  Nothing is
 // freed by hand.
@@ -50,6 +50,7 @@ struct sq_phi4_ens {
     sq::DevBuf<int> flags;               // [R]
     sq::PinBuf<double> series;           // the last step call's records, written by the kernel
     sq::DevBuf<double> mom;              // [R][5]
+    sq::DevBuf<unsigned long long> dig;  // [R] sq_phi4_ensemble_digest's device buffer (first digest on)
     bool rec_dirty = true;               // the device records are behind rep[]
     std::vector<sq::Phi4EnsFrameState> fst;  // [R] frame state, current between calls
     sq::DevBuf<sq::Phi4EnsFrameState> fst_dev;
@@ -157,6 +158,11 @@ int ens_step(sq_phi4_ens *e, int nsteps, int every, double *series, int measure,
 int ens_run_frames(sq_phi4_ens *e, int nframes, int *stable, double *dtau, double *series, int measure, int scheme);
 
 // ---- sq_phi4_ens_corr.cpp ----
+// What stands against momenta on a lattice of this shape, nullptr where they run (sq_phi4_ens_set_momenta, a load).
+const char *ens_momenta_shape_error(int sites, int Lz);
+// sq_phi4_ens_set_momenta behind its checks: the tables, the layout, the accumulators zeroed.  Only an allocation
+// or the runtime can fail it; M = 0 is applied on any shape (a load of a handle without momenta).
+int ens_apply_momenta(sq_phi4_ens *e, int M, const int *nxy);
 Phi4EnsCorrArgs ens_corr_args(const sq_phi4_ens *e);
 // The handle's momenta for a launch; corr: the zero-momentum accumulators advance as well.
 Phi4EnsPCorrArgs ens_pcorr_args(const sq_phi4_ens *e, bool corr);
@@ -171,6 +177,8 @@ void ens_replica_stats(const sq_phi4_ens *e, const double *G, size_t stride, con
 Phi4EnsFlowArgs ens_flow_args(const sq_phi4_ens *e);
 // Bring the device's flow records up to rep[] and the flow parameters (the stream is idle).
 int ens_sync_flow(sq_phi4_ens *e);
+// sq_phi4_ens_set_flow behind its checks (fm2, flam NaN: each replica's own); only an allocation can fail it.
+int ens_apply_flow(sq_phi4_ens *e, double eps, int nlevels, const int *levels, double fm2, double flam);
 
 }  // namespace sq
 #pragma GCC visibility pop

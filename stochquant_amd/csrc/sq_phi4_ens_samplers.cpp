@@ -4,6 +4,8 @@
 // run trajectories and one of the latter round by round without leaving the stream.
 #include "sq_phi4_ens_host.h"
 
+#include "sq_phi4_ens_ckpt_format.h"
+
 using namespace sq;
 
 // ---- MALA ----
@@ -233,8 +235,7 @@ extern "C" {
 
 int sq_phi4_ens_set_ladder(sq_phi4_ens *e, int nlad) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
-    if (nlad != 0 && (nlad < 2 || nlad > e->R || e->R % nlad != 0))
-        return fail(SQ_E_ARG, "nlad must be 0 (no ladders) or lie in [2, nrep] and divide nrep");
+    if (const char *why = sq::ckpt::ladder_error(nlad, e->R)) return fail(SQ_E_ARG, why);
     e->nlad = nlad;
     return SQ_OK;
 }

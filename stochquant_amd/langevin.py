@@ -1599,6 +1599,64 @@ class Phi4Ensemble:
         _lib.call("sq_phi4_ens_perf", self._h, ctypes.byref(p))
         return {k: getattr(p, k) for k, _ in p._fields_}
 
+    def digest(self, first=0, count=None):
+        """(count,) uint64: the field digest of replicas first .. first + count, computed on the device
+        (sq_phi4_ensemble_digest): the wrapping sum over sites i of mix(i << 32 | bits32(phi[i])), mix the
+        splitmix64 finaliser.  Two fields have one digest exactly when they agree bit for bit (up to 2^-64);
+        nothing is moved but eight bytes per replica, and nothing changes."""
+        k = self._count(first, count)
+        d = np.zeros(max(k, 0), dtype=np.uint64)
+        _lib.call("sq_phi4_ensemble_digest", self._h, int(first), k, d.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)))
+        return d
+
+    def save(self, path):
+        """Checkpoint the whole ensemble as `path` (.npy: np.load(path) is download()), `path`.state and
+        `path`.json (sq_phi4_ensemble_save): fields, seeds, counters, Δτ, parameters, frame state, settings,
+        every accumulator and every sampler statistic.  The handle goes on as one that never saved."""
+        _lib.call("sq_phi4_ensemble_save", self._h, os.fsencode(path))
+
+    def load(self, path, fields_only=False):
+        """Resume from the checkpoint `path` (sq_phi4_ensemble_load): shape, replicas, loops, clamp and adapt_dtau
+        must be this ensemble's; everything else, the seeds included, comes from the files, and the run goes on
+        bit for bit as the saver would have.  Every file is validated first: a refused load (StochQuantError)
+        changes nothing.  fields_only: only shape and replicas must match, and only the fields are taken."""
+        _lib.call("sq_phi4_ensemble_load", self._h, os.fsencode(path), 1 if fields_only else 0)
+        if not fields_only:
+            self._frames_run = self._has_frame_records()  # as on the handle that saved
+
+    def _has_frame_records(self):
+        """Whether the handle holds a last frame's records: sq_phi4_ens_stability takes n = 1 exactly then."""
+        one = [np.zeros(1, dtype=np.float32) for _ in range(3)]
+        rc = _lib.load().sq_phi4_ens_stability(self._h, 0, 0, None, None, *[_fptr(a) for a in one], 1)
+        return rc == _lib.SQ_OK
+
+    @staticmethod
+    def checkpoint_info(path, verify=False):
+        """The identity of the checkpoint `path` (sq_phi4_ensemble_checkpoint_info; no device, no handle):
+        {"version", "shape", "replicas", "loops", "adapt_dtau", "sections", "clamp"}.  verify: also read the other
+        two files and run every check of a load that needs no handle.  Raises StochQuantError (SQ_E_ARG) for a
+        set of files a load would refuse."""
+        info = (ctypes.c_longlong * 8)()
+        clamp = ctypes.c_double()
+        _lib.call("sq_phi4_ensemble_checkpoint_info", os.fsencode(path), 1 if verify else 0, info, ctypes.byref(clamp))
+        v = [int(x) for x in info]
+        return {"version": v[0], "shape": (v[1], v[2], v[3]), "replicas": v[4], "loops": v[5],
+                "adapt_dtau": bool(v[6]), "sections": v[7], "clamp": clamp.value}
+
+    @classmethod
+    def restore(cls, path, device=0):
+        """A new ensemble of the checkpoint's identity, loaded from it."""
+        i = cls.checkpoint_info(path)
+        # placeholder parameters any clamp admits; the load brings the saved ones
+        e = cls(i["shape"], i["replicas"], dtau=1e-30, m2=0.0, lam=0.0, C=0.0, clamp=i["clamp"], device=device,
+                loops=i["loops"], adapt_dtau=i["adapt_dtau"])
+        try:
+            e.load(path)
+        except Exception:
+            e.close()
+            raise
+        return e
+
 
 def connect_p2p(lat, group=None):
     """All-gather the ranks' P2P handle blobs over torch.distributed and connect."""
