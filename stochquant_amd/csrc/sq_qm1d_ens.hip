@@ -177,8 +177,10 @@ __global__ __launch_bounds__(MW ? 1024 : HELP ? 64 * (1 + kHelpWaves) : 64) void
     const int runs = (int)runs_ll;
     const uint32_t k0 = R->k0, k1 = R->k1;
     const double h = dtau;
-    const double sig = A.C * (double)__fsqrt_rn((float)(2. * dtau / A.a));
-    const double sigw = A.C * (double)__fsqrt_rn((float)(2. * dtau));
+    // sqrtf is the correctly rounded root, as the host's; __fsqrt_rn is v_sqrt_f32 alone
+    // here, an ulp off for some Δτ (0.00465 for one)
+    const double sig = A.C * (double)sqrtf((float)(2. * dtau / A.a));
+    const double sigw = A.C * (double)sqrtf((float)(2. * dtau));
     const double a = A.a;
     const UDiv da2 = udiv_prep(A.a2);
     const double ninf = -__builtin_inf();
