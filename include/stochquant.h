@@ -765,6 +765,44 @@ int sq_phi4_ens_step_hmc(sq_phi4_ens *e, int ntraj, int nleap, int randomize, in
 int sq_phi4_ens_hmc_stats(sq_phi4_ens *e, int first, int count, long long *out /*[count][4]*/);
 int sq_phi4_ens_hmc_reset(sq_phi4_ens *e, int first, int count);
 
+/* HMC trajectories of the single phi^4 lattice: a PHI4 context of one periodic
+ * slab (comm none), any shape sq_create accepts, the field in device memory
+ * (DESIGN.md §4.4).  ABI 6: symbols added, none changed.
+ *
+ * The trajectory is the ensemble's, points 1 - 6 of the block above, with the
+ * context's dtau, m2, lambda, C, clamp and seed as the record and sq_get_step's
+ * counter as s: replica r of an ensemble and a context with that replica's
+ * parameters walk the same chain -- fields, u, L and verdicts bit for bit.
+ * What differs is point 4's ORDER OF SUMMATION, so dH agrees up to the rounding
+ * of its double sums: a lane adds its sites' terms in the order of its march
+ * (planes ascending, then rows, then x), a wave's lanes and a block's waves are
+ * summed in a fixed order, each block stores one double, and the verdict adds
+ * the blocks' doubles in 256 contiguous runs of ascending block index, the runs
+ * in order, the first pass's total before the last one's.  No atomics: the bits
+ * of dH depend on the lattice shape alone, not on the call nor on how calls
+ * are split.
+ *
+ * sq_phi4_step_hmc: ntraj trajectories, enqueued as one stream of launches with
+ * no host round trip between them; the call waits only to return rec
+ * ([ntraj][4] = dH, u, verdict, L; nullable).  Errors, all before any device
+ * work: a null context, ntraj < 0, nleap outside [1, SQ_PHI4_ENS_MAX_LEAP]:
+ * SQ_E_ARG; a QM1D context, a slab context (comm other than none), sigma =
+ * (float)(C sqrt(2 dtau)) equal to 0, a pending sticky error: SQ_E_STATE.
+ * ntraj = 0 does nothing after the checks.  The counter advances by one per
+ * trajectory; trajectories, sq_step and the frame calls alternate freely;
+ * sq_perf counts one step per trajectory and sites x L site updates.  The first
+ * call allocates one more field buffer.
+ *
+ * sq_phi4_hmc_stats: out = {trajectories, accepted, guard trips, leapfrog
+ * steps} since creation or the last sq_phi4_hmc_reset.  A verdict 2 keeps phi_0
+ * bit for bit, counts as a guard trip and sets the context's HMC guard flag,
+ * which only sq_phi4_hmc_reset clears (frames keep their own flag per frame).
+ * The statistics are not part of sq_save_field. */
+int sq_phi4_step_hmc(sq_ctx *ctx, int ntraj, int nleap, int randomize,
+                     double *rec /*[ntraj][4] = dH, u, verdict, L; nullable*/);
+int sq_phi4_hmc_stats(sq_ctx *ctx, long long out[4]);
+int sq_phi4_hmc_reset(sq_ctx *ctx);
+
 /* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
  * replicas of a ladder swap their fields with a Metropolis test, decided and
  * carried out on the device.  ABI 6: symbols added, none

@@ -229,6 +229,9 @@ SIGNATURES = {
     "sq_phi4_ens_step_hmc": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
     "sq_phi4_ens_hmc_stats": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ens_hmc_reset": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int]),
+    "sq_phi4_step_hmc": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D]),
+    "sq_phi4_hmc_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_hmc_reset": (ctypes.c_int, [_P]),
     "sq_phi4_ens_set_ladder": (ctypes.c_int, [_P, ctypes.c_int]),
     "sq_phi4_ens_get_ladder": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     "sq_phi4_ens_exchange_round": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -164,6 +164,7 @@ int sq_destroy(sq_ctx *c) {
     release_slabs(c);
     release_qm1d_serial(c);
     release_frames(c);
+    release_hmc(c);
     release_lattice(c);
     release_qm1d(c);
     release_events(c);

@@ -271,6 +271,17 @@ struct Phi4Frames {
     sq::FrameCtl *ctl_cur = nullptr;
 };
 
+// ---- sq_phi4_hmc.cpp: HMC trajectories of a single periodic slab, allocated at the first trajectory call ----
+struct Phi4HmcState;
+struct Phi4Hmc {
+    float *hmc_q = nullptr;          // the trajectory's second buffer, padded like Slab::buf (the first is the idle one)
+    double *hmc_part = nullptr;      // 2 x hmc_nblocks per-block sums of the two term passes
+    int hmc_nblocks = 0;
+    sq::Phi4HmcState *hmc_st = nullptr;
+    double *hmc_rec = nullptr;       // a call's record rows on the device
+    size_t hmc_rec_cap = 0;          // ... in rows
+};
+
 // ---- sq_comm.cpp ----
 struct P2pHost {
     ncclComm_t comm = nullptr;
@@ -302,8 +313,8 @@ struct ProfHost {
 
 }  // namespace sq
 
-struct sq_ctx : sq::Qm1dHost, sq::Qm1dSerialHost, sq::Phi4Lattice, sq::Phi4Schedule, sq::Phi4Frames, sq::P2pHost,
-                sq::ProfHost {
+struct sq_ctx : sq::Qm1dHost, sq::Qm1dSerialHost, sq::Phi4Lattice, sq::Phi4Schedule, sq::Phi4Frames, sq::Phi4Hmc,
+                sq::P2pHost, sq::ProfHost {
     sq_params p{};
     int dev = 0;
     double dtau = 0;
@@ -360,6 +371,13 @@ int gate_reset(sq_ctx *c);
 int fin_agree(sq_ctx *c);
 int phi4_steps(sq_ctx *c, int n);
 int phi4_join(sq_ctx *c);
+// single periodic slab: the launch arguments of one step from buffer cur into the other, and that launch
+// (the plain one-step kernel; nothing flipped, nothing counted but the launch)
+sq::Phi4StepArgs phi4_periodic_args(sq_ctx *c);
+int phi4_periodic_launch(sq_ctx *c);
+
+// sq_phi4_hmc.cpp
+void release_hmc(sq_ctx *c);
 
 // sq_phi4_frames.cpp
 int alloc_frame_records(sq_ctx *c);

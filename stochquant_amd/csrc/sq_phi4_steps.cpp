@@ -267,9 +267,7 @@ int phi4_tb2_run_pairs(sq_ctx *c, int pairs) {
 
 // Single slab covering the lattice: one launch per step, z wraps in-kernel.
 int phi4_periodic_step(sq_ctx *c) {
-    Slab &s = c->slabs[0];
-    const int nzc = (s.nz + c->zc - 1) / c->zc;
-    int rc = phi4_launch_range(c, s, c->cur, s.sA, 0, s.nz, c->zc, c->zc, nzc, 1, true);
+    int rc = phi4_periodic_launch(c);
     if (rc) return rc;
     c->cur ^= 1;
     count_step(c);
@@ -664,6 +662,24 @@ int phi4_steps_impl(sq_ctx *c, int n) {
 }  // namespace
 
 namespace sq {
+
+sq::Phi4StepArgs phi4_periodic_args(sq_ctx *c) {
+    const Slab &s = c->slabs[0];
+    sq::Phi4StepArgs a = phi4_base_args(c, s, c->cur);
+    a.zlo = 0;
+    a.zhi = s.nz;
+    a.zstep = c->zc;
+    a.zc = c->zc;
+    a.nzc = (s.nz + c->zc - 1) / c->zc;
+    a.periodic = 1;
+    sq::phi4_fill_units(a, c->geom);
+    return a;
+}
+
+int phi4_periodic_launch(sq_ctx *c) {
+    const Slab &s = c->slabs[0];
+    return phi4_launch_range(c, s, c->cur, s.sA, 0, s.nz, c->zc, c->zc, (s.nz + c->zc - 1) / c->zc, 1, true);
+}
 
 // P2P: does the block's last pair write the next exchange's staging slot
 // (SQ_P2P_KSTAGE pins it; by default with the exchange on stream A, whose

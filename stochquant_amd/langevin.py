@@ -388,6 +388,25 @@ class Phi4Lattice(_Ctx):
     def step(self, n=1):
         _lib.call("sq_step", self._h, int(n))
 
+    def step_hmc(self, n=1, nleap=1, randomize=False, record=False):
+        """n hybrid Monte Carlo trajectories of nleap leapfrog steps (randomize: lengths uniform on
+        1 .. nleap) on a comm="none" lattice: the ensemble's trajectory, bit for bit, with the field in
+        device memory (sq_phi4_step_hmc).  record: returns the (n, 4) array of dH, u, verdict (0
+        rejected, 1 accepted, 2 guard trip), L; else None, without waiting for the device."""
+        rec = np.zeros((int(n), 4), dtype=np.float64) if record else None
+        _lib.call("sq_phi4_step_hmc", self._h, int(n), int(nleap), 1 if randomize else 0,
+                  _dptr(rec) if record else None)
+        return rec
+
+    def hmc_stats(self):
+        """[trajectories, accepted, guard trips, leapfrog steps] since creation or hmc_reset()."""
+        out = np.zeros(4, dtype=np.int64)
+        _lib.call("sq_phi4_hmc_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def hmc_reset(self):
+        _lib.call("sq_phi4_hmc_reset", self._h)
+
     def upload(self, phi):
         a = np.ascontiguousarray(phi, dtype=np.float32)
         if a.size != int(np.prod(self.local_shape)):
