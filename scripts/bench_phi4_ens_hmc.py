@@ -33,11 +33,13 @@ smallest window W >= 20 τ_int, ρ averaged over the replicas; and the products
 τ_int x wall time per update.
 
 --parent-lib: the existing calls must not move.  step(steps), step(steps,
-scheme="heun"), step(steps, scheme="mala") and run_frames(50) at 32³ R = 256
-with this build and with another build of the library (SQ_LIB), in interleaved
-rounds of child processes, the other build first and then twice in a row as
-well: the spread of the other build against itself is the allowance.
-Writes profiles/r07/phi4_ens_hmc/bench.json.
+scheme="heun"), step(steps, scheme="mala") and run_frames(50) at 32³ R = 256,
+and step_hmc(steps) at nleap = 1, 10 and 10 randomised at the three cases
+above (Δτ the case's first guess), with this build and with another build of
+the library (SQ_LIB), in interleaved rounds of child processes, the other build
+first and then twice in a row as well: the spread of the other build against
+itself is the allowance.
+Writes profiles/r07/phi4_ens_hmc/bench.json unless --out names another file.
 """
 import argparse
 import json
@@ -254,8 +256,18 @@ def raw_worker(steps, reps):
         ens.init_field(0.5)
         ens.run_frames(FRAMES)
         frames = statistics.median(_timed(lambda: ens.run_frames(FRAMES)) for _ in range(reps))
-    print(json.dumps({"euler_ms": round(euler, 4), "heun_ms": round(heun, 4), "mala_ms": round(mala, 4),
-                      "frames_ms": round(frames, 4), "build_id": _lib.build_id()}), flush=True)
+    out = {"euler_ms": round(euler, 4), "heun_ms": round(heun, 4), "mala_ms": round(mala, 4),
+           "frames_ms": round(frames, 4)}
+    for shape, R, dtau in CASES:
+        with Phi4Ensemble(shape, R, seed=7, dtau=dtau, **PARAMS) as ens:
+            ens.init_field(0.5)
+            ens.step(THERMALISE)
+            for name, call in (("hmc1", dict(nleap=1)), ("hmc10", dict(nleap=NLEAP)),
+                               ("hmc10r", dict(nleap=NLEAP, randomize=True))):
+                ens.step_hmc(steps, **call)
+                out[f"{name}_{shape[0]}_ms"] = round(statistics.median(_timed(lambda: ens.step_hmc(steps, **call))
+                                                                       for _ in range(reps)), 4)
+    print(json.dumps(dict(out, build_id=_lib.build_id())), flush=True)
 
 
 def _child(args, timeout, env=None):
@@ -319,7 +331,7 @@ def main():
         ab = {"kind": "existing_calls_vs_parent", "shape": [32, 32, 32], "R": 256, "steps": a.steps, "nframes": FRAMES,
               "pairs": pairs, "parent_build_id": pairs[0]["parent"]["build_id"],
               "this_build_id": pairs[0]["this"]["build_id"]}
-        for k in ("euler_ms", "heun_ms", "mala_ms", "frames_ms"):
+        for k in [k for k in pairs[0]["parent"] if k.endswith("_ms")]:
             d = [(p["this"][k] / p["parent"][k] - 1.0) * 100.0 for p in pairs]
             s = [(p["parent_again"][k] / p["parent"][k] - 1.0) * 100.0 for p in pairs]
             ab[k[:-3]] = {"parent_median_ms": round(statistics.median(p["parent"][k] for p in pairs), 4),

@@ -22,7 +22,8 @@ MALA step evaluates the drift twice in double and takes a decision (one fold,
 one more barrier), and it drops Heun's second noise application.
 
 --parent-lib: the existing calls must not move.  step(steps), step(steps,
-scheme="heun") and run_frames(50) at 32³ R = 256 with this build and with
+scheme="heun") and run_frames(50) at 32³ R = 256, and step(steps,
+scheme="mala") at the three cases above, with this build and with
 another build of the library (SQ_LIB), in interleaved rounds of child
 processes, the other build first and then twice in a row as well: the spread
 of the other build against itself is the allowance.
@@ -113,8 +114,15 @@ def raw_worker(steps, reps):
         ens.init_field(0.5)
         ens.run_frames(FRAMES)
         frames = statistics.median(_timed(lambda: ens.run_frames(FRAMES)) for _ in range(reps))
-    print(json.dumps({"euler_ms": round(euler, 4), "heun_ms": round(heun, 4), "frames_ms": round(frames, 4),
-                      "build_id": _lib.build_id()}), flush=True)
+    out = {"euler_ms": round(euler, 4), "heun_ms": round(heun, 4), "frames_ms": round(frames, 4)}
+    for shape, R, dtau in CASES:
+        with Phi4Ensemble(shape, R, seed=7, dtau=dtau, **PARAMS) as ens:
+            ens.init_field(0.5)
+            ens.step(THERMALISE)
+            ens.step(steps, scheme="mala")
+            out[f"mala{shape[0]}_ms"] = round(statistics.median(_timed(lambda: ens.step(steps, scheme="mala"))
+                                                                for _ in range(reps)), 4)
+    print(json.dumps(dict(out, build_id=_lib.build_id())), flush=True)
 
 
 def _child(args, timeout, env=None):
@@ -164,7 +172,7 @@ def main():
         ab = {"kind": "existing_calls_vs_parent", "shape": [32, 32, 32], "R": 256, "steps": a.steps, "nframes": FRAMES,
               "pairs": pairs, "parent_build_id": pairs[0]["parent"]["build_id"],
               "this_build_id": pairs[0]["this"]["build_id"]}
-        for k in ("euler_ms", "heun_ms", "frames_ms"):
+        for k in [k for k in pairs[0]["parent"] if k.endswith("_ms")]:
             d = [(p["this"][k] / p["parent"][k] - 1.0) * 100.0 for p in pairs]
             s = [(p["parent_again"][k] / p["parent"][k] - 1.0) * 100.0 for p in pairs]
             ab[k[:-3]] = {"parent_median_ms": round(statistics.median(p["parent"][k] for p in pairs), 4),

@@ -61,7 +61,7 @@
 // A measurement point puts one more barrier in front of its own use of the
 // scratch (ens_fold), since a slow wave may still be folding the step's totals.
 #include "sq_phi4_ens_launch.h"
-#include "sq_phi4_ens_mala_dev.h"  // MalaCoef, mala_site, mala_quad
+#include "sq_phi4_ens_mala_dev.h"  // MalaCoef, mala_site, mala_quad, mala_verdict
 
 namespace sq {
 
@@ -189,13 +189,9 @@ __global__ __launch_bounds__(kPhi4EnsMaxLanes) void phi4_ens_mala_kernel(const P
         // every lane holds the same values: scalars, so that the branches below are the block's
         const double dH = readlane_d(0.5 * tot / sig2, 0);
         mx = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(mx)));
-        const u32x4 o = philox4x32_10(u32x4{0u, kStreamAccept << 24, slo, shi}, rc.k0, rc.k1);
-        const double u = ((double)o.x + 0.5) * 0x1p-32;
-        int v = 0;
-        if (mx >= E.clampv) v = 2;
-        else if (dH <= 0.0) v = 1;
-        else if (u < exp(-dH)) v = 1;  // false for a NaN dH
-        v = __builtin_amdgcn_readfirstlane(v);
+        double u;
+        const int v = __builtin_amdgcn_readfirstlane(mala_verdict(
+            dH, [&] { return mx >= E.clampv; }, slo, shi, rc.k0, rc.k1, u));
         nacc += v == 1;
         ngrd += v == 2;
         if (threadIdx.x == 0 && W.rec != nullptr) {

@@ -1,7 +1,7 @@
 // sq_phi4_ens_mala_dev.h -- the device functions the Metropolis kernels share
-// (sq_phi4_ens_mala.hip, sq_phi4_ens_hmc.hip): the per-site
-// term of 2 sig^2 dH in double.  The head of sq_phi4_ens_mala.hip states the
-// term and the order of summation.
+// (sq_phi4_ens_mala.hip, sq_phi4_ens_hmc.hip, sq_phi4_hmc.hip):
+// the per-site term of 2 sig^2 dH in double, and the test behind it.  The head
+// of sq_phi4_ens_mala.hip states the term and the order of summation.
 #pragma once
 #include "sq_phi4_ens_dev.h"
 
@@ -60,6 +60,22 @@ __device__ __forceinline__ MalaCoef mala_coef(const Phi4EnsRec &rc) {
     M.km = readlane_d(3.0 + 0.5 * M.m2, 0);
     M.l4 = readlane_d(0.25 * M.lam6, 0);
     return M;
+}
+
+// The Metropolis test of the step or trajectory at counter s under the replica's key: u from word 0 of the
+// Philox block at {0, kStreamAccept << 24, s lo, s hi}; verdict 2 where the guard tripped, 1 (accepted) where
+// dH <= 0 or u < exp(-dH), else 0: a NaN dH rejects.  tripped: a callable that returns the flag, asked behind the
+// Philox block, where the ensemble kernels have always compared their guard maximum with the clamp.
+template <class Tripped>
+__device__ __forceinline__ int mala_verdict(double dH, Tripped tripped, uint32_t slo, uint32_t shi, uint32_t k0,
+                                            uint32_t k1, double &u) {
+    const u32x4 o = philox4x32_10(u32x4{0u, kStreamAccept << 24, slo, shi}, k0, k1);
+    u = ((double)o.x + 0.5) * 0x1p-32;
+    int v = 0;
+    if (tripped()) v = 2;
+    else if (dH <= 0.0) v = 1;
+    else if (u < exp(-dH)) v = 1;  // false for a NaN dH
+    return v;
 }
 
 }  // namespace

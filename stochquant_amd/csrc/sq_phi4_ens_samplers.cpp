@@ -1,71 +1,30 @@
 // sq_phi4_ens_samplers.cpp -- the phi^4 ensemble's exact samplers: the Metropolis-adjusted Langevin step
-// (sq_phi4_ens_mala.hip), hybrid Monte Carlo trajectories (sq_phi4_ens_hmc.hip), replica exchange
-// (sq_phi4_ens_exchange.hip), Swendsen-Wang cluster sweeps (sq_phi4_ens_cluster.hip), and the two calls that
-// run trajectories and one of the latter round by round without leaving the stream.
+// (sq_phi4_ens_mala.hip) and hybrid Monte Carlo trajectories (sq_phi4_ens_hmc.hip), which share one host path,
+// replica exchange (sq_phi4_ens_exchange.hip), Swendsen-Wang cluster sweeps (sq_phi4_ens_cluster.hip), and the
+// two calls that run trajectories and one of the latter round by round without leaving the stream.
 #include "sq_phi4_ens_host.h"
 
 #include "sq_phi4_ens_ckpt_format.h"
 
 using namespace sq;
 
-// ---- MALA ----
-extern "C" {
-
-int sq_phi4_ens_step_mala(sq_phi4_ens *e, int nsteps, int every, double *series, int measure, double *rec) {
-    if (!e) return fail(SQ_E_ARG, "null ensemble");
-    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
-    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a MALA step measures no momenta");
-    if (measure ? every < 1 : every < 0)
-        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
-    int rc = ens_needs_noise(e, "a MALA step", "without noise there is no proposal density");
-    if (rc || nsteps == 0) return rc;
-    const bool corr = (measure & 1) != 0;
-    DeviceGuard g(e->dev);
-    const size_t nrec = (every > 0 && series) ? (size_t)(nsteps / every) : 0;
-    const size_t nd = nrec * (size_t)e->R * 4;
-    const size_t nm = rec ? (size_t)nsteps * (size_t)e->R * 3 : 0;
-    rc = ens_sync_recs(e);
-    if (!rc) rc = ens_zeroed(e->mstat, 3 * (size_t)e->R);
-    if (!rc) rc = ens_reserve(e->series, nd);
-    if (!rc) rc = ens_reserve(e->mrec, nm);
-    if (rc) return rc;
-    sq::Phi4EnsArgs a = ens_args(e);
-    a.nsteps = nsteps;
-    a.every = (nd || corr) ? every : 0;
-    a.series = nd ? e->series.data() : nullptr;
-    sq::Phi4EnsMalaArgs w{};
-    w.stat = e->mstat.data();
-    w.rec = nm ? e->mrec.data() : nullptr;
-    const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
-    SQ_HIP(sq::phi4_ens_mala_launch(a, w, corr ? &c : nullptr, e->R, e->stream));
-    e->launches++;
-    SQ_HIP(hipStreamSynchronize(e->stream));
-    if (nd) memcpy(series, e->series.data(), sizeof(double) * nd);
-    if (nm) memcpy(rec, e->mrec.data(), sizeof(double) * nm);
-    ens_advance(e, (unsigned long long)nsteps);
-    return SQ_OK;
-}
-
-int sq_phi4_ens_mala_stats(sq_phi4_ens *e, int first, int count, long long *out) {
-    return ens_read_rows(e, &sq_phi4_ens::mstat, 3, first, count, out);  // no MALA step yet: zeros
-}
-
-int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count) {
-    return ens_clear_rows(e, &sq_phi4_ens::mstat, 3, first, count);
-}
-
-}  // extern "C"
-
-// ---- HMC ----
+// ---- MALA and HMC ----
 namespace {
 
-// The arguments of sq_phi4_ens_step_hmc, which the fused calls repeat round by round.
-struct EnsHmc {
+// The arguments of sq_phi4_ens_step_hmc, which the fused calls repeat round by round, and (hmc off: ntraj steps,
+// nleap and randomize not used) of sq_phi4_ens_step_mala.  The sampler names its counters, its records and
+// their width.
+struct EnsTraj {
     int ntraj, nleap, randomize, every, measure;
     double *series, *rec;  // nullable
+    bool hmc = true;
+    size_t width() const { return hmc ? 4 : 3; }
+    sq::DevBuf<long long> &stat(sq_phi4_ens *e) const { return hmc ? e->hstat : e->mstat; }
+    sq::PinBuf<double> &recs(sq_phi4_ens *e) const { return hmc ? e->hrec : e->mrec; }
 };
 
-int ens_hmc_check(const EnsHmc &h) {
+// The trajectories' argument rules (h.hmc set: sq_phi4_ens_step_mala checks its own arguments, with its own messages).
+int ens_hmc_check(const EnsTraj &h) {
     if (h.ntraj < 0) return fail(SQ_E_ARG, "ntraj must be >= 0");
     if (h.nleap < 1 || h.nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap must lie in [1, 4096]");
     if (h.measure & ~1)
@@ -75,8 +34,8 @@ int ens_hmc_check(const EnsHmc &h) {
     return SQ_OK;
 }
 
-// The fused calls' rule on top.
-int ens_hmc_fused_check(int nrounds, const EnsHmc &h) {
+// The fused calls' rule on top; they run trajectories only (h.hmc set).
+int ens_hmc_fused_check(int nrounds, const EnsTraj &h) {
     if (nrounds < 0) return fail(SQ_E_ARG, "nrounds must be >= 0");
     int rc = ens_hmc_check(h);
     if (rc) return rc;
@@ -86,19 +45,19 @@ int ens_hmc_fused_check(int nrounds, const EnsHmc &h) {
 }
 
 // One round's series and per-trajectory records, in doubles.
-size_t ens_hmc_series(const sq_phi4_ens *e, const EnsHmc &h) {
+size_t ens_traj_series(const sq_phi4_ens *e, const EnsTraj &h) {
     return (h.every > 0 && h.series) ? (size_t)(h.ntraj / h.every) * (size_t)e->R * 4 : 0;
 }
-size_t ens_hmc_recs(const sq_phi4_ens *e, const EnsHmc &h) {
-    return h.rec ? (size_t)h.ntraj * (size_t)e->R * 4 : 0;
+size_t ens_traj_recs(const sq_phi4_ens *e, const EnsTraj &h) {
+    return h.rec ? (size_t)h.ntraj * (size_t)e->R * h.width() : 0;
 }
 
 // Before the first launch of nrounds rounds: the device records, the counters, room for what the kernels write.
-int ens_hmc_prepare(sq_phi4_ens *e, int nrounds, const EnsHmc &h) {
+int ens_traj_prepare(sq_phi4_ens *e, int nrounds, const EnsTraj &h) {
     int rc = ens_sync_recs(e);
-    if (!rc) rc = ens_zeroed(e->hstat, 4 * (size_t)e->R);
-    if (!rc) rc = ens_reserve(e->series, ens_hmc_series(e, h) * (size_t)nrounds);
-    if (!rc) rc = ens_reserve(e->hrec, ens_hmc_recs(e, h) * (size_t)nrounds);
+    if (!rc) rc = ens_zeroed(h.stat(e), h.width() * (size_t)e->R);
+    if (!rc) rc = ens_reserve(e->series, ens_traj_series(e, h) * (size_t)nrounds);
+    if (!rc) rc = ens_reserve(h.recs(e), ens_traj_recs(e, h) * (size_t)nrounds);
     return rc;
 }
 
@@ -106,14 +65,16 @@ int ens_hmc_prepare(sq_phi4_ens *e, int nrounds, const EnsHmc &h) {
 // the series and records to the caller.  A failed enqueue ends the loop; the stream is synchronised all the same.
 // The caller advances the counters.
 template <class Behind>
-int ens_hmc_rounds(sq_phi4_ens *e, int nrounds, const EnsHmc &h, Behind behind) {
+int ens_traj_rounds(sq_phi4_ens *e, int nrounds, const EnsTraj &h, Behind behind) {
     const bool corr = (h.measure & 1) != 0;
-    const size_t per = ens_hmc_series(e, h), perh = ens_hmc_recs(e, h);
+    const size_t per = ens_traj_series(e, h), perh = ens_traj_recs(e, h);
     const size_t nd = per * (size_t)nrounds, nm = perh * (size_t)nrounds;
-    sq::Phi4EnsHmcArgs w{};
-    w.stat = e->hstat.data();
-    w.nleap = h.nleap;
-    w.randomize = h.randomize != 0 ? 1 : 0;
+    sq::Phi4EnsMalaArgs wm{};
+    wm.stat = e->mstat.data();
+    sq::Phi4EnsHmcArgs wh{};
+    wh.stat = e->hstat.data();
+    wh.nleap = h.nleap;
+    wh.randomize = h.randomize != 0 ? 1 : 0;
     const sq::Phi4EnsCorrArgs c = ens_corr_args(e);
     int rc = SQ_OK;
     for (int i = 0; i < nrounds && !rc; ++i) {
@@ -123,10 +84,12 @@ int ens_hmc_rounds(sq_phi4_ens *e, int nrounds, const EnsHmc &h, Behind behind) 
             a.nsteps = h.ntraj;
             a.every = (nd || corr) ? h.every : 0;
             a.series = nd ? e->series.data() + per * (size_t)i : nullptr;
-            w.rec = nm ? e->hrec.data() + perh * (size_t)i : nullptr;
-            const hipError_t he = sq::phi4_ens_hmc_launch(a, w, corr ? &c : nullptr, e->R, e->stream);
+            wm.rec = wh.rec = nm ? h.recs(e).data() + perh * (size_t)i : nullptr;
+            const hipError_t he = h.hmc ? sq::phi4_ens_hmc_launch(a, wh, corr ? &c : nullptr, e->R, e->stream)
+                                        : sq::phi4_ens_mala_launch(a, wm, corr ? &c : nullptr, e->R, e->stream);
             if (he != hipSuccess) {
-                rc = fail(SQ_E_HIP, std::string("phi4_ens_hmc_launch: ") + hipGetErrorString(he));
+                rc = fail(SQ_E_HIP, std::string(h.hmc ? "phi4_ens_hmc_launch: " : "phi4_ens_mala_launch: ") +
+                                        hipGetErrorString(he));
                 break;
             }
             e->launches++;
@@ -137,7 +100,17 @@ int ens_hmc_rounds(sq_phi4_ens *e, int nrounds, const EnsHmc &h, Behind behind) 
     if (rc) return rc;
     SQ_HIP(he);
     if (nd) memcpy(h.series, e->series.data(), sizeof(double) * nd);
-    if (nm) memcpy(h.rec, e->hrec.data(), sizeof(double) * nm);
+    if (nm) memcpy(h.rec, h.recs(e).data(), sizeof(double) * nm);
+    return SQ_OK;
+}
+
+// One round with nothing behind it, and the counter advanced by one per trajectory.
+int ens_traj_call(sq_phi4_ens *e, const EnsTraj &h) {
+    DeviceGuard g(e->dev);
+    int rc = ens_traj_prepare(e, 1, h);
+    if (!rc) rc = ens_traj_rounds(e, 1, h, [](int) { return SQ_OK; });
+    if (rc) return rc;
+    ens_advance(e, (unsigned long long)h.ntraj);
     return SQ_OK;
 }
 
@@ -145,19 +118,33 @@ int ens_hmc_rounds(sq_phi4_ens *e, int nrounds, const EnsHmc &h, Behind behind) 
 
 extern "C" {
 
+int sq_phi4_ens_step_mala(sq_phi4_ens *e, int nsteps, int every, double *series, int measure, double *rec) {
+    if (!e) return fail(SQ_E_ARG, "null ensemble");
+    if (nsteps < 0) return fail(SQ_E_ARG, "nsteps must be >= 0");
+    if (measure & ~1) return fail(SQ_E_ARG, "measure holds bit 0 (correlator) only: a MALA step measures no momenta");
+    if (measure ? every < 1 : every < 0)
+        return fail(SQ_E_ARG, measure ? "a correlator measurement needs every >= 1" : "every must be >= 0");
+    int rc = ens_needs_noise(e, "a MALA step", "without noise there is no proposal density");
+    if (rc || nsteps == 0) return rc;
+    return ens_traj_call(e, EnsTraj{nsteps, 1, 0, every, measure, series, rec, false});
+}
+
+int sq_phi4_ens_mala_stats(sq_phi4_ens *e, int first, int count, long long *out) {
+    return ens_read_rows(e, &sq_phi4_ens::mstat, 3, first, count, out);  // no MALA step yet: zeros
+}
+
+int sq_phi4_ens_mala_reset(sq_phi4_ens *e, int first, int count) {
+    return ens_clear_rows(e, &sq_phi4_ens::mstat, 3, first, count);
+}
+
 int sq_phi4_ens_step_hmc(sq_phi4_ens *e, int ntraj, int nleap, int randomize, int every, double *series, int measure,
                          double *rec) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
-    const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec};
+    const EnsTraj h{ntraj, nleap, randomize, every, measure, series, rec};
     int rc = ens_hmc_check(h);
     if (!rc) rc = ens_needs_noise(e, "a trajectory", "without noise there is no momentum to draw");
     if (rc || ntraj == 0) return rc;
-    DeviceGuard g(e->dev);
-    rc = ens_hmc_prepare(e, 1, h);
-    if (!rc) rc = ens_hmc_rounds(e, 1, h, [](int) { return SQ_OK; });
-    if (rc) return rc;
-    ens_advance(e, (unsigned long long)ntraj);  // one count per trajectory
-    return SQ_OK;
+    return ens_traj_call(e, h);
 }
 
 int sq_phi4_ens_hmc_stats(sq_phi4_ens *e, int first, int count, long long *out) {
@@ -279,15 +266,15 @@ int sq_phi4_ens_exchange(sq_phi4_ens *e, int nrounds, double *rec) {
 int sq_phi4_ens_step_hmc_exchange(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
                                   double *series, int measure, double *rec_hmc, double *rec_x) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
-    const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
+    const EnsTraj h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
     int rc = ens_hmc_fused_check(nrounds, h);
     if (!rc) rc = ens_xchg_state(e);  // the trajectories' C != 0 as well
     if (rc || nrounds == 0) return rc;
     DeviceGuard g(e->dev);
     std::vector<int> lab;
-    rc = ens_hmc_prepare(e, nrounds, h);
+    rc = ens_traj_prepare(e, nrounds, h);
     if (!rc) rc = ens_xchg_begin(e, rec_x ? (size_t)nrounds * (size_t)e->R * 5 : 0, lab);
-    if (!rc) rc = ens_hmc_rounds(e, nrounds, h, [&](int i) { return ens_xchg_enqueue(e, i, rec_x != nullptr); });
+    if (!rc) rc = ens_traj_rounds(e, nrounds, h, [&](int i) { return ens_xchg_enqueue(e, i, rec_x != nullptr); });
     if (rc) return rc;
     ens_xchg_end(e, nrounds, rec_x, lab);
     ens_advance(e, (unsigned long long)nrounds * (unsigned long long)ntraj);  // one count per trajectory
@@ -431,7 +418,7 @@ int ens_cluster(sq_phi4_ens *e, int nsweeps, unsigned char *bonds, int *labels, 
 }
 
 // sq_phi4_ens_step_hmc_cluster and, x non-null, its _improved form.
-int ens_hmc_cluster(sq_phi4_ens *e, int nrounds, const EnsHmc &h, unsigned char *bonds, int *labels,
+int ens_hmc_cluster(sq_phi4_ens *e, int nrounds, const EnsTraj &h, unsigned char *bonds, int *labels,
                     const EnsSums *x) {
     if (!e) return fail(SQ_E_ARG, "null ensemble");
     int rc = ens_hmc_fused_check(nrounds, h);
@@ -440,10 +427,10 @@ int ens_hmc_cluster(sq_phi4_ens *e, int nrounds, const EnsHmc &h, unsigned char 
     if (!rc) rc = ens_cluster_state(e);  // the trajectories' C != 0 as well
     if (rc || nrounds == 0) return rc;
     DeviceGuard g(e->dev);
-    rc = ens_hmc_prepare(e, nrounds, h);
+    rc = ens_traj_prepare(e, nrounds, h);
     if (!rc) rc = ens_cluster_bufs(e, nrounds, bonds != nullptr, labels != nullptr, x);
     if (!rc)
-        rc = ens_hmc_rounds(e, nrounds, h,
+        rc = ens_traj_rounds(e, nrounds, h,
                             [&](int i) { return ens_cluster_enqueue(e, i, bonds != nullptr, labels != nullptr, x); });
     if (!rc) rc = ens_cluster_end(e, nrounds, bonds, labels, x);
     if (rc) return rc;
@@ -479,14 +466,14 @@ int sq_phi4_ensemble_cluster_improved(sq_phi4_ens *e, int nsweeps, double *serie
 
 int sq_phi4_ens_step_hmc_cluster(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
                                  double *series, int measure, double *rec_hmc, unsigned char *bonds, int *labels) {
-    const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
+    const EnsTraj h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
     return ens_hmc_cluster(e, nrounds, h, bonds, labels, nullptr);
 }
 
 int sq_phi4_ensemble_step_hmc_cluster_improved(sq_phi4_ens *e, int nrounds, int ntraj, int nleap, int randomize, int every,
                                           double *series, int measure, double *rec_hmc, unsigned char *bonds,
                                           int *labels, double *cseries, long long *weights) {
-    const EnsHmc h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
+    const EnsTraj h{ntraj, nleap, randomize, every, measure, series, rec_hmc};
     const EnsSums x{cseries, weights};
     return ens_hmc_cluster(e, nrounds, h, bonds, labels, &x);
 }

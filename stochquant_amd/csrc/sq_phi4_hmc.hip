@@ -44,7 +44,7 @@
 // The trip word: a lane whose running max of |g| and |phi_{k+1}| (or |phi_1|)
 // reaches the clamp stores 1 to it, a plain store of the same value by every
 // such lane.  The verdict reads and clears it.  No kernel here draws normals.
-#include "sq_phi4_ens_mala_dev.h"  // mala_quad, mala_coef; sq_phi4.hip's device functions through sq_phi4_ens_dev.h
+#include "sq_phi4_ens_mala_dev.h"  // mala_quad, mala_coef, mala_verdict; sq_phi4.hip's device functions through sq_phi4_ens_dev.h
 #include "sq_phi4_hmc.h"
 
 namespace sq {
@@ -277,12 +277,8 @@ __global__ __launch_bounds__(kVerdictLanes) void phi4_hmc_verdict_kernel(const P
     if (threadIdx.x != 0) return;
     const double sig2 = (double)W.sig * (double)W.sig;
     const double dH = 0.5 * (sub + add) / sig2;
-    const u32x4 o = philox4x32_10(u32x4{0u, kStreamAccept << 24, W.s_lo, W.s_hi}, W.k0, W.k1);
-    const double u = ((double)o.x + 0.5) * 0x1p-32;
-    int v = 0;
-    if (W.st->trip != 0) v = 2;
-    else if (dH <= 0.0) v = 1;
-    else if (u < exp(-dH)) v = 1;  // false for a NaN dH
+    double u;
+    const int v = mala_verdict(dH, [&] { return W.st->trip != 0; }, W.s_lo, W.s_hi, W.k0, W.k1, u);
     if (W.rec != nullptr) {
         W.rec[0] = dH;
         W.rec[1] = u;
