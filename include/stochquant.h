@@ -803,6 +803,84 @@ int sq_phi4_step_hmc(sq_ctx *ctx, int ntraj, int nleap, int randomize,
 int sq_phi4_hmc_stats(sq_ctx *ctx, long long out[4]);
 int sq_phi4_hmc_reset(sq_ctx *ctx);
 
+/* Swendsen-Wang cluster sweeps of the single phi^4 lattice: the non-local move
+ * beside sq_phi4_step_hmc, for any lattice below 2^31 sites, the field in
+ * device memory.  ABI 6: symbols added, none changed.
+ *
+ * The sweep is the ensemble's, points 1 - 6 of the block above
+ * sq_phi4_ens_cluster, with h = (float)dtau, sig = (float)(C sqrt(2 h)) and the
+ * context's seed halves as the record and the key, and the context's own
+ * cluster-sweep counter as c (0 at creation; sq_phi4_cluster_sweep,
+ * sq_phi4_set_cluster_sweep).  The definition does not depend on the
+ * algorithm: a context and replica 0 of an ensemble with the same seed,
+ * parameters, field and counter produce the same bonds, labels, field and
+ * statistics, bit for bit.  Only sign bits of the field change; the step
+ * counter, dtau, the HMC statistics, the stability state and what the step
+ * kernels cache about the field (it stays inside the guard: |phi| is kept) are
+ * untouched.
+ *
+ * Launch sequence of one sweep, on the slab's step stream, nothing read back
+ * inside or between sweeps, no kernel waiting for another work-group:
+ *   1. bonds and labels per brick of tx x ty x tz sites in LDS (one work-group
+ *      each, partial last bricks in y and z): the bond byte of every site and
+ *      the global index of its root inside the brick go to device memory;
+ *   2. every on-bond that leaves its brick, periodic wraps included, united in
+ *      the label array by atomic minima (links point from the larger index to
+ *      the smaller, so chains fall strictly and every loop has a written
+ *      bound: DESIGN.md §4.5);
+ *   3. every site chases its chain to the root, which is its label; flips from
+ *      the root's Philox word; the counts as integers, any order the same.
+ * A brick whose labelling reached its bound of sites-in-brick + 1 passes, or a
+ * union that reached its bound of 2 sites + 2 steps, raises a device word: the
+ * sweep then writes no field word and counts as one unconverged sweep.  Both
+ * bounds are what the worst case needs, so the count stays 0.  Beside the field
+ * a context that sweeps holds 5 more bytes per site (a label, a bond byte),
+ * allocated at the first sweep call.
+ *
+ * Limits, each refused before anything is launched: a null context, nsweeps or
+ * nrounds < 0 (and sq_phi4_step_hmc's argument errors): SQ_E_ARG; a QM1D
+ * context, a slab context (comm other than none), sigma equal to 0 (C = 0 has
+ * no beta), 2^31 sites or more (labels are 32-bit), a pending sticky error:
+ * SQ_E_STATE.  Alone the sweep is not ergodic (|phi| is frozen): alternate it
+ * with trajectories on thermalised fields.
+ *
+ * sq_phi4_cluster: nsweeps sweeps at counters c, c + 1, ..  bonds
+ * ([nsweeps][sites] bytes, bits 0 .. 2 = the forward bonds x, y, z) and labels
+ * ([nsweeps][sites]), both nullable, in the ensemble's encoding: stream-ordered
+ * device copies per sweep, one read-back at the end.  Without them the call
+ * does not wait for the device.
+ *
+ * sq_phi4_step_hmc_cluster: per round ntraj trajectories of sq_phi4_step_hmc
+ * and one sweep, all enqueued back to back; the call waits once, and only to
+ * return records (rec_hmc [nrounds ntraj][4], bonds and labels
+ * [nrounds][sites], all nullable).  Bit for bit the loop
+ * { sq_phi4_step_hmc(ntraj, ..); sq_phi4_cluster(1, ..) }.
+ *
+ * sq_phi4_cluster_stats: out = {sweeps, clusters, flipped clusters, flipped
+ * sites, unconverged sweeps} since creation or the last sq_phi4_cluster_reset.
+ * Neither they nor the counter are part of sq_save_field: a resume sets the
+ * counter with sq_phi4_set_cluster_sweep.
+ *
+ * sq_phi4_cluster_shape_info: out = {tx, ty, tz, bricks in x, y, z, LDS bytes
+ * of launch 1, device bytes per site beside the field} for a context of these
+ * dims; needs no device; SQ_E_ARG for the dims sq_create refuses or 2^31 sites
+ * or more.  SQ_CLUSTER_TILE=tx,ty,tz (a tuning override, read when a context
+ * sets its sweep state up and by this call) replaces the brick where tx is a
+ * power of two in [8, 256] that divides Lx, ty and tz are positive (cut to Ly
+ * and Lz) and the brick holds at most 8192 sites; anything else is ignored. */
+int sq_phi4_cluster(sq_ctx *ctx, int nsweeps,
+                    unsigned char *bonds /*[nsweeps][sites], bits 0..2 = x, y, z forward; nullable*/,
+                    int *labels /*[nsweeps][sites]; nullable*/);
+int sq_phi4_step_hmc_cluster(sq_ctx *ctx, int nrounds, int ntraj, int nleap, int randomize,
+                             double *rec_hmc /*[nrounds ntraj][4], nullable*/,
+                             unsigned char *bonds /*[nrounds][sites], nullable*/,
+                             int *labels /*[nrounds][sites], nullable*/);
+int sq_phi4_cluster_stats(sq_ctx *ctx, long long out[5]);
+int sq_phi4_cluster_reset(sq_ctx *ctx);
+int sq_phi4_cluster_sweep(sq_ctx *ctx, unsigned long long *c);
+int sq_phi4_set_cluster_sweep(sq_ctx *ctx, unsigned long long c);
+int sq_phi4_cluster_shape_info(const long long dims[3], int out[8]);
+
 /* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
  * replicas of a ladder swap their fields with a Metropolis test, decided and
  * carried out on the device.  ABI 6: symbols added, none

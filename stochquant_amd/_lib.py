@@ -232,7 +232,15 @@ SIGNATURES = {
     "sq_phi4_step_hmc": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D]),
     "sq_phi4_hmc_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_hmc_reset": (ctypes.c_int, [_P]),
-    "sq_phi4_ens_set_ladder": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sq_phi4_cluster": (ctypes.c_int, [_P, ctypes.c_int, ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_step_hmc_cluster": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D,
+                                                ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_cluster_stats": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_cluster_reset": (ctypes.c_int, [_P]),
+    "sq_phi4_cluster_sweep": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),
+    "sq_phi4_set_cluster_sweep": (ctypes.c_int, [_P, ctypes.c_ulonglong]),
+    "sq_phi4_cluster_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_ens_set_ladder":(ctypes.c_int, [_P, ctypes.c_int]),
     "sq_phi4_ens_get_ladder": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     "sq_phi4_ens_exchange_round": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),
     "sq_phi4_ens_set_exchange_round": (ctypes.c_int, [_P, ctypes.c_ulonglong]),

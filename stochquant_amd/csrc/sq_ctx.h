@@ -282,6 +282,20 @@ struct Phi4Hmc {
     size_t hmc_rec_cap = 0;          // ... in rows
 };
 
+// ---- sq_phi4_cluster.cpp: cluster sweeps of a single periodic slab, allocated at the first sweep call ----
+struct Phi4ClusterState;
+struct Phi4Cluster {
+    uint32_t *clu_label = nullptr;   // one label per site
+    uint8_t *clu_bonds = nullptr;    // one bond byte per site
+    sq::Phi4ClusterState *clu_st = nullptr;
+    int clu_tile[3] = {0, 0, 0};     // the brick, chosen when the state is set up (SQ_CLUSTER_TILE read then)
+    unsigned long long clu_sweep = 0;  // the Philox counter of the next sweep (sq_phi4_cluster_sweep)
+    unsigned long long clu_seq = 0;    // sweeps enqueued so far: the parity of the trip word
+    uint8_t *clu_rec_bonds = nullptr;  // a call's records on the device, clu_rec_cap sweeps each
+    int *clu_rec_labels = nullptr;
+    size_t clu_rec_cap = 0;
+};
+
 // ---- sq_comm.cpp ----
 struct P2pHost {
     ncclComm_t comm = nullptr;
@@ -314,7 +328,7 @@ struct ProfHost {
 }  // namespace sq
 
 struct sq_ctx : sq::Qm1dHost, sq::Qm1dSerialHost, sq::Phi4Lattice, sq::Phi4Schedule, sq::Phi4Frames, sq::Phi4Hmc,
-                sq::P2pHost, sq::ProfHost {
+                sq::Phi4Cluster, sq::P2pHost, sq::ProfHost {
     sq_params p{};
     int dev = 0;
     double dtau = 0;
@@ -378,6 +392,15 @@ int phi4_periodic_launch(sq_ctx *c);
 
 // sq_phi4_hmc.cpp
 void release_hmc(sq_ctx *c);
+// sq_phi4_step_hmc in parts: every check; the buffers and `rows` record rows; ntraj trajectories enqueued, their
+// records to rows row0 ..; the rows' copy to the host enqueued
+int phi4_hmc_check(sq_ctx *c, int ntraj, int nleap);
+int phi4_hmc_reserve(sq_ctx *c, size_t rows);
+int phi4_hmc_enqueue(sq_ctx *c, int ntraj, int nleap, int randomize, size_t row0, bool rec);
+int phi4_hmc_fetch(sq_ctx *c, double *rec, size_t rows);
+
+// sq_phi4_cluster.cpp
+void release_cluster(sq_ctx *c);
 
 // sq_phi4_frames.cpp
 int alloc_frame_records(sq_ctx *c);

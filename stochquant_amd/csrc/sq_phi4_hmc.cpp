@@ -140,6 +140,35 @@ int hmc_trajectory(sq_ctx *c, int L, float sig, double *rec_row) {
 
 namespace sq {
 
+// sq_phi4_step_hmc in its parts, which sq_phi4_step_hmc_cluster (sq_phi4_cluster.cpp) puts a sweep between.
+int phi4_hmc_check(sq_ctx *c, int ntraj, int nleap) {
+    if (!c) return fail(SQ_E_ARG, "null context");
+    if (ntraj < 0) return fail(SQ_E_ARG, "ntraj < 0");
+    if (nleap < 1 || nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap outside [1, SQ_PHI4_ENS_MAX_LEAP]");
+    int rc = hmc_ctx_check(c);
+    if (rc) return rc;
+    if (hmc_sigma(c) == 0.0f) return fail(SQ_E_STATE, "HMC trajectories need noise: sigma = C sqrt(2 dtau) is 0");
+    DeviceGuard g(c->dev);
+    return gate_check(c, false);  // a pending sticky error: no trajectories on a corrupt field
+}
+
+int phi4_hmc_reserve(sq_ctx *c, size_t rows) { return hmc_alloc(c, phi4_periodic_args(c), rows); }
+
+int phi4_hmc_enqueue(sq_ctx *c, int ntraj, int nleap, int randomize, size_t row0, bool rec) {
+    const float sig = hmc_sigma(c);
+    for (int t = 0; t < ntraj; ++t) {
+        int rc = hmc_trajectory(c, hmc_length(c, nleap, randomize), sig,
+                                rec ? c->hmc_rec + 4 * (row0 + (size_t)t) : nullptr);
+        if (rc) return rc;
+    }
+    return SQ_OK;
+}
+
+int phi4_hmc_fetch(sq_ctx *c, double *rec, size_t rows) {
+    SQ_HIP(hipMemcpyAsync(rec, c->hmc_rec, rows * 4 * sizeof(double), hipMemcpyDeviceToHost, c->slabs[0].sA));
+    return SQ_OK;
+}
+
 void release_hmc(sq_ctx *c) {
     (void)hipFree(c->hmc_q);
     (void)hipFree(c->hmc_part);
@@ -157,28 +186,14 @@ void release_hmc(sq_ctx *c) {
 extern "C" {
 
 int sq_phi4_step_hmc(sq_ctx *c, int ntraj, int nleap, int randomize, double *rec) {
-    if (!c) return fail(SQ_E_ARG, "null context");
-    if (ntraj < 0) return fail(SQ_E_ARG, "ntraj < 0");
-    if (nleap < 1 || nleap > SQ_PHI4_ENS_MAX_LEAP) return fail(SQ_E_ARG, "nleap outside [1, SQ_PHI4_ENS_MAX_LEAP]");
-    int rc = hmc_ctx_check(c);
-    if (rc) return rc;
-    const float sig = hmc_sigma(c);
-    if (sig == 0.0f) return fail(SQ_E_STATE, "HMC trajectories need noise: sigma = C sqrt(2 dtau) is 0");
+    int rc = phi4_hmc_check(c, ntraj, nleap);
+    if (rc || ntraj == 0) return rc;
     DeviceGuard g(c->dev);
-    rc = gate_check(c, false);  // a pending sticky error: no trajectories on a corrupt field
+    rc = phi4_hmc_reserve(c, rec ? (size_t)ntraj : 0);
+    if (!rc) rc = phi4_hmc_enqueue(c, ntraj, nleap, randomize, 0, rec != nullptr);
+    if (!rc && rec) rc = phi4_hmc_fetch(c, rec, (size_t)ntraj);
     if (rc) return rc;
-    if (ntraj == 0) return SQ_OK;
-    rc = hmc_alloc(c, phi4_periodic_args(c), rec ? (size_t)ntraj : 0);
-    if (rc) return rc;
-    for (int t = 0; t < ntraj; ++t) {
-        rc = hmc_trajectory(c, hmc_length(c, nleap, randomize), sig, rec ? c->hmc_rec + 4 * (size_t)t : nullptr);
-        if (rc) return rc;
-    }
-    if (rec) {
-        hipStream_t st = c->slabs[0].sA;
-        SQ_HIP(hipMemcpyAsync(rec, c->hmc_rec, (size_t)ntraj * 4 * sizeof(double), hipMemcpyDeviceToHost, st));
-        SQ_HIP(hipStreamSynchronize(st));
-    }
+    if (rec) SQ_HIP(hipStreamSynchronize(c->slabs[0].sA));
     return SQ_OK;
 }
 

@@ -407,6 +407,76 @@ class Phi4Lattice(_Ctx):
     def hmc_reset(self):
         _lib.call("sq_phi4_hmc_reset", self._h)
 
+    def _cluster_records(self, n, record):
+        sites = int(np.prod(self.local_shape))
+        if not record:
+            return None, None
+        return np.zeros((n, sites), dtype=np.uint8), np.zeros((n, sites), dtype=np.int32)
+
+    def cluster(self, sweeps=1, record=False):
+        """`sweeps` Swendsen-Wang cluster sweeps on a comm="none" lattice below 2^31 sites: the ensemble's
+        sweep (`Phi4Ensemble.cluster`), bit for bit, with the field in device memory and the labelling
+        across work-groups (sq_phi4_cluster; include/stochquant.h has the definition and the launch
+        sequence).  Sweep k of the call draws at the counter `cluster_sweep` + k.  Only sign bits of the
+        field change.  record=True: returns (bonds, labels), the (sweeps, sites) uint8 array of the
+        sites' forward bonds (bits 0, 1, 2 = x, y, z) and the (sweeps, sites) int32 array of their
+        cluster labels; else None, without waiting for the device.  Needs C != 0 (StochQuantError
+        otherwise).  Alone the sweep is not ergodic: alternate it with trajectories
+        (`step_hmc_cluster`).  Neither the counter nor `cluster_stats()` are part of `save`: a resume
+        sets `cluster_sweep`."""
+        sweeps = int(sweeps)
+        bonds, labels = self._cluster_records(max(sweeps, 0), record)
+        _lib.call("sq_phi4_cluster", self._h, sweeps,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
+        return (bonds, labels) if record else None
+
+    def step_hmc_cluster(self, rounds, ntraj=1, nleap=1, randomize=False, record=False):
+        """`rounds` times: `step_hmc(ntraj, nleap, randomize)`, then one `cluster` sweep, all enqueued
+        back to back (sq_phi4_step_hmc_cluster): bit for bit the loop of the two calls.  record=True:
+        returns (rec_hmc, bonds, labels), the (rounds * ntraj, 4) records of `step_hmc` and the
+        (rounds, sites) records of `cluster`, after one synchronisation; else None without one."""
+        rounds, ntraj = int(rounds), int(ntraj)
+        nr, nj = max(rounds, 0), max(ntraj, 0)
+        rh = np.zeros((nr * nj, 4), dtype=np.float64) if record else None
+        bonds, labels = self._cluster_records(nr, record)
+        _lib.call("sq_phi4_step_hmc_cluster", self._h, rounds, ntraj, int(nleap), 1 if randomize else 0,
+                  _dptr(rh) if record and rh.size else None,
+                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
+        return (rh, bonds, labels) if record else None
+
+    def cluster_stats(self):
+        """[sweeps, clusters, flipped clusters, flipped sites, unconverged sweeps] since creation or
+        cluster_reset()."""
+        out = np.zeros(5, dtype=np.int64)
+        _lib.call("sq_phi4_cluster_stats", self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)))
+        return out
+
+    def cluster_reset(self):
+        _lib.call("sq_phi4_cluster_reset", self._h)
+
+    @property
+    def cluster_sweep(self):
+        """The 64-bit counter the next cluster sweep draws its Philox blocks at."""
+        c = ctypes.c_ulonglong()
+        _lib.call("sq_phi4_cluster_sweep", self._h, ctypes.byref(c))
+        return c.value
+
+    @cluster_sweep.setter
+    def cluster_sweep(self, v):
+        _lib.call("sq_phi4_set_cluster_sweep", self._h, ctypes.c_ulonglong(int(v)))
+
+    @staticmethod
+    def cluster_shape_info(shape):
+        """Without a device: {"tile": (tx, ty, tz), "tiles": bricks per axis, "lds": LDS bytes of the
+        labelling launch, "bytes_per_site": device bytes beside the field} of the cluster sweeps of a
+        lattice of `shape` (sq_phi4_cluster_shape_info; SQ_CLUSTER_TILE=tx,ty,tz overrides the brick)."""
+        dims = (ctypes.c_longlong * 3)(*[int(s) for s in shape])
+        out = (ctypes.c_int * 8)()
+        _lib.call("sq_phi4_cluster_shape_info", dims, out)
+        return {"tile": tuple(out[0:3]), "tiles": tuple(out[3:6]), "lds": out[6], "bytes_per_site": out[7]}
+
     def upload(self, phi):
         a = np.ascontiguousarray(phi, dtype=np.float32)
         if a.size != int(np.prod(self.local_shape)):
