@@ -881,6 +881,100 @@ int sq_phi4_cluster_sweep(sq_ctx *ctx, unsigned long long *c);
 int sq_phi4_set_cluster_sweep(sq_ctx *ctx, unsigned long long c);
 int sq_phi4_cluster_shape_info(const long long dims[3], int out[8]);
 
+/* In-stream measurements of a single phi^4 lattice (one periodic slab, comm
+ * none; other contexts get SQ_E_STATE before anything is launched; DESIGN.md
+ * §4.6).  ABI 6: symbols added, none changed.  What the ensemble reports
+ * through every=, correlate= and momenta=, for a field in device memory: one
+ * measurement is three launches on the slab's step stream (march, fold,
+ * correlator), the host reads nothing between them and no launch uses an
+ * atomic.
+ *
+ * One measurement of the current field phi gives
+ *   S1 = sum phi, S2 = sum phi^2, S4 = sum phi^4,
+ *   NN = sum_x phi(x) (phi(x + ex) + phi(x + ey) + phi(x + ez))   (periodic),
+ *   S(z) = sum_{x,y} phi(x, y, z); with momenta set, A_m(z) + i B_m(z) =
+ *   sum_{x,y} phi e^{i (px x + py y)} from the tables of
+ *   sq_phi4_ens_momentum_table, by the four-line recipe stated above
+ *   sq_phi4_ens_set_momenta with the y-twiddle applied to a row's sums,
+ *   g(t) = sum_z S(z) S((z + t) mod Lz), g_m(t) = sum_z [A A' + B B'],
+ *   t = 0 .. nt - 1, nt = Lz / 2 + 1; nothing is divided by V.
+ *
+ * Summation order.  Every value is a double, every product and sum rounded
+ * once (no fused multiply-add).  The step kernel's tile: a wave owns an x-span
+ * of 4 QX V sites and 64 / QX row groups of R rows per lane (sq_phi4_tile); a
+ * lane's quads of a row are v = 0 .. V - 1 at x0 = span + 4 (lane mod QX) + 4
+ * QX v, values p0 .. p3, r right of p3, d0 .. d3 the row below, n0 .. n3 the
+ * next plane.  Per plane and row: rs = 0.0, rs += (p0 + p1) + (p2 + p3) per
+ * quad; the row's QX lanes by a butterfly (level k = 1, 2, 4, .. QX / 2: every
+ * lane adds its partner's value, the partner being lane ^ 1, lane ^ 2, the
+ * lane mirrored in its group of 8, mirrored in its row of 16, lane ^ 16, lane
+ * ^ 32: the balanced tree over the lanes in lane order); t = 0.0, t += rs per
+ * row, r ascending; t over the row groups by the butterfly's remaining levels.
+ * A_m, B_m: per row re = 0.0, im = 0.0, re += (p0 cx[x0] + p1 cx[x0+1]) + (p2
+ * cx[x0+2] + p3 cx[x0+3]) per quad, im with sx; both over the row's lanes; a =
+ * 0.0, b = 0.0, a += re cy[y] - im sy[y], b += re sy[y] + im cy[y] per row;
+ * then over the row groups.  These per-plane values of a wave's unit are
+ * stored, and S(z), A_m(z), B_m(z) are their sums over the plane's units in the
+ * order x-span + (spans per row) row-group ascending, from 0.0.  S2, S4, NN:
+ * one double per lane over its z-chunk of zc planes, planes ascending, then
+ * rows, then v: S2 += (p0^2 + p1^2) + (p2^2 + p3^2), S4 += (p0^2 p0^2 + p1^2
+ * p1^2) + (p2^2 p2^2 + p3^2 p3^2), NN += (((p0 p1 + p1 p2) + (p2 p3 + p3 r)) +
+ * ((p0 d0 + p1 d1) + (p2 d2 + p3 d3))) + ((p0 n0 + p1 n1) + (p2 n2 + p3 n3));
+ * the wave by all six butterfly levels; the units' totals in 256 contiguous
+ * runs of ceil(units / 256), unit ascending within a run from 0.0, then the
+ * runs in order from 0.0.  S1 = S(z) added z ascending from 0.0.  g(t) and
+ * g_m(t): z ascending from acc = 0.0, acc = acc + S S' and acc = (acc + A A')
+ * + B B'.  The bits of every result depend on the shape and the field alone,
+ * not on the call, on how calls are split, or on whether the measurement ran
+ * in flight or stand-alone.  For a finite field, momentum (0, 0) gives A(z) =
+ * S(z) bit for bit and B(z) = +0.0, and g_m = g.
+ *
+ * sq_phi4_set_momenta / sq_phi4_get_momenta: the argument rules of
+ * sq_phi4_ens_set_momenta (0 <= M <= SQ_PHI4_ENS_MAX_MOMENTA, 0 <= nx < Lx, 0
+ * <= ny < Ly, duplicates allowed; SQ_E_ARG otherwise); a new context has M =
+ * 0.  Every call waits for the step stream and zeroes Gp and nmeas_p, as the
+ * ensemble's setter does.
+ *
+ * sq_phi4_measure: one measurement of the current field, accumulating
+ * nothing: sums4 = {S1, S2, S4, NN}, S [Lz], AB [M][Lz][2] = {A, B}, g [nt], gp
+ * [M][nt]; every output nullable; AB or gp with M = 0: SQ_E_STATE.
+ *
+ * sq_phi4_step_hmc_meas: as sq_phi4_step_hmc for fields, records, counters and
+ * statistics; additionally one measurement of the field behind the commit of
+ * each every-th trajectory of the call (every >= 1, else SQ_E_ARG; an
+ * incomplete tail measures nothing).  measure bit 0: G[t] = G[t] + g(t), S1acc
+ * = S1acc + S1, nmeas += 1; bit 1: Gp[m][t] = Gp[m][t] + g_m(t), nmeas_p += 1;
+ * one addition each, so calls split in any way add up to the same bits.  Other
+ * bits: SQ_E_ARG; bit 1 with M = 0: SQ_E_STATE.  series (nullable): (ntraj /
+ * every) rows {S1, S2, S4, NN}, read back once at the end with the records.
+ * sq_phi4_step_hmc_cluster_meas: the same behind the sweep of each every-th
+ * round of sq_phi4_step_hmc_cluster; series has (nrounds / every) rows.
+ *
+ * sq_phi4_corr_sums: the raw accumulators G [nt], S1acc, nmeas, Gp [M][nt],
+ * nmeas_p (any may be NULL): persistent device memory, zero at creation,
+ * cleared by sq_phi4_corr_reset (and Gp, nmeas_p by sq_phi4_set_momenta) only.
+ * Neither the accumulators nor the momenta are part of sq_save_field.
+ *
+ * sq_phi4_measure_shape_info (no device): out = {units per plane, bytes of the
+ * per-plane partial array [Lz][units per plane][1 + 2 M] doubles, dynamic LDS
+ * bytes of the correlator launch (8 Lz, with momenta 16 Lz; 0 where that
+ * exceeds 64 KiB and the slices are read from device memory), nt} for the
+ * default tile of these dims; SQ_E_ARG for the dims sq_create refuses and for
+ * M outside [0, SQ_PHI4_ENS_MAX_MOMENTA]. */
+int sq_phi4_set_momenta(sq_ctx *ctx, int M, const int *nxy /*[M][2] = nx, ny*/);
+int sq_phi4_get_momenta(sq_ctx *ctx, int *M, int *nxy);
+int sq_phi4_measure(sq_ctx *ctx, double *sums4, double *S /*[Lz]*/, double *AB /*[M][Lz][2]*/, double *g /*[nt]*/,
+                    double *gp /*[M][nt]*/);
+int sq_phi4_step_hmc_meas(sq_ctx *ctx, int ntraj, int nleap, int randomize, int every,
+                          double *series /*[ntraj / every][4], nullable*/, int measure,
+                          double *rec /*[ntraj][4], nullable*/);
+int sq_phi4_step_hmc_cluster_meas(sq_ctx *ctx, int nrounds, int ntraj, int nleap, int randomize, int every,
+                                  double *series /*[nrounds / every][4], nullable*/, int measure,
+                                  double *rec_hmc, unsigned char *bonds, int *labels);
+int sq_phi4_corr_sums(sq_ctx *ctx, double *G, double *S1, long long *nmeas, double *Gp, long long *nmeas_p);
+int sq_phi4_corr_reset(sq_ctx *ctx);
+int sq_phi4_measure_shape_info(const long long dims[3], int M, long long out[4]);
+
 /* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
  * replicas of a ladder swap their fields with a Metropolis test, decided and
  * carried out on the device.  ABI 6: symbols added, none

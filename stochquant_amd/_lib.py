@@ -240,6 +240,17 @@ SIGNATURES = {
     "sq_phi4_cluster_sweep": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),
     "sq_phi4_set_cluster_sweep": (ctypes.c_int, [_P, ctypes.c_ulonglong]),
     "sq_phi4_cluster_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_set_momenta": (ctypes.c_int, [_P, ctypes.c_int, _I]),
+    "sq_phi4_get_momenta": (ctypes.c_int, [_P, _I, _I]),
+    "sq_phi4_measure": (ctypes.c_int, [_P, _D, _D, _D, _D, _D]),
+    "sq_phi4_step_hmc_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
+    "sq_phi4_step_hmc_cluster_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                     _D, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_ubyte),
+                                                     ctypes.POINTER(ctypes.c_int)]),
+    "sq_phi4_corr_sums": (ctypes.c_int, [_P, _D, _D, ctypes.POINTER(ctypes.c_longlong), _D, ctypes.POINTER(ctypes.c_longlong)]),
+    "sq_phi4_corr_reset": (ctypes.c_int, [_P]),
+    "sq_phi4_measure_shape_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int,
+                                                  ctypes.POINTER(ctypes.c_longlong)]),
     "sq_phi4_ens_set_ladder":(ctypes.c_int, [_P, ctypes.c_int]),
     "sq_phi4_ens_get_ladder": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_int)]),
     "sq_phi4_ens_exchange_round": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -166,6 +166,7 @@ int sq_destroy(sq_ctx *c) {
     release_frames(c);
     release_hmc(c);
     release_cluster(c);
+    release_measure(c);
     release_lattice(c);
     release_qm1d(c);
     release_events(c);

@@ -296,6 +296,21 @@ struct Phi4Cluster {
     size_t clu_rec_cap = 0;
 };
 
+// ---- sq_phi4_measure.cpp: in-stream measurements of a single periodic slab, allocated at the first use ----
+struct Phi4Measure {
+    int mz_M = 0;                              // momenta set (sq_phi4_set_momenta)
+    int mz_n[2 * SQ_PHI4_ENS_MAX_MOMENTA] = {};  // their (nx, ny)
+    double *mz_tab = nullptr;     // twiddle tables: cx | sx [8][Lx], cy | sy [8][Ly]
+    double *mz_part = nullptr;    // the march's per-plane partials [nz][units per plane][1 + 2 M]
+    size_t mz_part_cap = 0;       // ... in doubles
+    double *mz_tot = nullptr;     // the march's per-unit totals [nunits][3]
+    int mz_nunits = 0;
+    double *mz_out = nullptr;     // one measurement's results: slices [17][nz] | sums [3] | row [4] | g [9][nt]
+    double *mz_acc = nullptr;     // the accumulators: G [nt] | Gp [8][nt] | S1 | nmeas, nmeas_p (64-bit integers)
+    double *mz_series = nullptr;  // a call's series rows on the device
+    size_t mz_series_cap = 0;     // ... in rows
+};
+
 // ---- sq_comm.cpp ----
 struct P2pHost {
     ncclComm_t comm = nullptr;
@@ -328,7 +343,7 @@ struct ProfHost {
 }  // namespace sq
 
 struct sq_ctx : sq::Qm1dHost, sq::Qm1dSerialHost, sq::Phi4Lattice, sq::Phi4Schedule, sq::Phi4Frames, sq::Phi4Hmc,
-                sq::Phi4Cluster, sq::P2pHost, sq::ProfHost {
+                sq::Phi4Cluster, sq::Phi4Measure, sq::P2pHost, sq::ProfHost {
     sq_params p{};
     int dev = 0;
     double dtau = 0;
@@ -401,6 +416,15 @@ int phi4_hmc_fetch(sq_ctx *c, double *rec, size_t rows);
 
 // sq_phi4_cluster.cpp
 void release_cluster(sq_ctx *c);
+// sq_phi4_step_hmc_cluster's sweep in parts: every check; the buffers and `rec_sweeps` record rows; one sweep
+// enqueued (rec >= 0: its records to that row); the rows' copies to the host enqueued
+int phi4_cluster_check(sq_ctx *c);
+int phi4_cluster_reserve(sq_ctx *c, size_t rec_sweeps);
+int phi4_cluster_enqueue(sq_ctx *c, long long rec);
+int phi4_cluster_fetch(sq_ctx *c, int n, unsigned char *bonds, int *labels);
+
+// sq_phi4_measure.cpp
+void release_measure(sq_ctx *c);
 
 // sq_phi4_frames.cpp
 int alloc_frame_records(sq_ctx *c);

@@ -146,6 +146,12 @@ Phi4ClusterTile phi4_cluster_tile(int Lx, int Ly, long long Lz, const char *spec
     return make_tile(Lx, Ly, Lz, tx, ty, tz);
 }
 
+// the sweep in its parts, which sq_phi4_step_hmc_cluster_meas (sq_phi4_measure.cpp) puts a measurement behind
+int phi4_cluster_check(sq_ctx *c) { return cluster_check(c); }
+int phi4_cluster_reserve(sq_ctx *c, size_t rec_sweeps) { return cluster_alloc(c, rec_sweeps); }
+int phi4_cluster_enqueue(sq_ctx *c, long long rec) { return cluster_sweep(c, rec); }
+int phi4_cluster_fetch(sq_ctx *c, int n, unsigned char *bonds, int *labels) { return cluster_fetch(c, n, bonds, labels); }
+
 void release_cluster(sq_ctx *c) {
     (void)hipFree(c->clu_label);
     (void)hipFree(c->clu_bonds);

@@ -388,15 +388,87 @@ class Phi4Lattice(_Ctx):
     def step(self, n=1):
         _lib.call("sq_step", self._h, int(n))
 
-    def step_hmc(self, n=1, nleap=1, randomize=False, record=False):
+    @staticmethod
+    def _measure_bits(every, correlate, momenta):
+        every = int(every)
+        if every < 1 and (correlate or momenta):
+            raise ValueError("correlate and momenta need every >= 1")
+        return every, (1 if correlate else 0) | (2 if momenta else 0)
+
+    def step_hmc(self, n=1, nleap=1, randomize=False, record=False, every=0, correlate=False, momenta=False):
         """n hybrid Monte Carlo trajectories of nleap leapfrog steps (randomize: lengths uniform on
         1 .. nleap) on a comm="none" lattice: the ensemble's trajectory, bit for bit, with the field in
         device memory (sq_phi4_step_hmc).  record: returns the (n, 4) array of dH, u, verdict (0
-        rejected, 1 accepted, 2 guard trip), L; else None, without waiting for the device."""
+        rejected, 1 accepted, 2 guard trip), L; else None, without waiting for the device.
+
+        every >= 1: one in-stream measurement (`measure`) behind each every-th trajectory, with no host
+        round trip (sq_phi4_step_hmc_meas); returns the (n // every, 4) series of `sums` rows, or
+        (series, records) with record.  correlate / momenta: the measurements also add to the
+        accumulators of `corr_sums()`."""
+        every, bits = self._measure_bits(every, correlate, momenta)
         rec = np.zeros((int(n), 4), dtype=np.float64) if record else None
-        _lib.call("sq_phi4_step_hmc", self._h, int(n), int(nleap), 1 if randomize else 0,
-                  _dptr(rec) if record else None)
-        return rec
+        if every < 1:
+            _lib.call("sq_phi4_step_hmc", self._h, int(n), int(nleap), 1 if randomize else 0,
+                      _dptr(rec) if record else None)
+            return rec
+        series = np.zeros((max(int(n), 0) // every, 4), dtype=np.float64)
+        _lib.call("sq_phi4_step_hmc_meas", self._h, int(n), int(nleap), 1 if randomize else 0, every,
+                  _dptr(series) if series.size else None, bits, _dptr(rec) if record else None)
+        return (series, rec) if record else series
+
+    def set_momenta(self, pairs):
+        """The spatial momenta (nx, ny), p = (2π nx / Lx, 2π ny / Ly), of `measure` and of the in-stream
+        measurements with momenta=True: at most 8, duplicates allowed (sq_phi4_set_momenta).  Zeroes
+        the momentum accumulators."""
+        a = np.ascontiguousarray(np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2))
+        _lib.call("sq_phi4_set_momenta", self._h, a.shape[0], a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+
+    @property
+    def momenta(self):
+        """The momenta set: a list of (nx, ny)."""
+        M = ctypes.c_int(0)
+        a = np.zeros((_lib.SQ_PHI4_ENS_MAX_MOMENTA, 2), dtype=np.int32)
+        _lib.call("sq_phi4_get_momenta", self._h, ctypes.byref(M), a.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+        return [(int(x), int(y)) for x, y in a[:M.value]]
+
+    def measure(self, slices=False):
+        """One measurement of the current field on the device, accumulating nothing (sq_phi4_measure;
+        include/stochquant.h states every sum's order): {"sums": [Σφ, Σφ², Σφ⁴, Σφ(x)(φ(x+ex) + φ(x+ey)
+        + φ(x+ez))]}; slices=True adds "S" (Lz,) the slice sums and "g" (nt,) their correlator, and with
+        momenta set "AB" (M, Lz, 2) the projections and "gp" (M, nt) their correlators."""
+        Lz, nt, M = self.shape[2], self.shape[2] // 2 + 1, len(self.momenta) if slices else 0
+        out = {"sums": np.zeros(4)}
+        if slices:
+            out["S"], out["g"] = np.zeros(Lz), np.zeros(nt)
+            if M:
+                out["AB"], out["gp"] = np.zeros((M, Lz, 2)), np.zeros((M, nt))
+        _lib.call("sq_phi4_measure", self._h, _dptr(out["sums"]), _dptr(out["S"]) if slices else None,
+                  _dptr(out["AB"]) if M else None, _dptr(out["g"]) if slices else None, _dptr(out["gp"]) if M else None)
+        return out
+
+    def corr_sums(self):
+        """The raw accumulators of the in-stream measurements: {"G" (nt,) = Σ g(t), "S1" = Σ Σφ, "nmeas",
+        "Gp" (M, nt) = Σ g_m(t), "nmeas_p"}; zero at creation, cleared by `corr_reset()` (and the
+        momentum pair by `set_momenta`) only; not part of `save`."""
+        nt, M = self.shape[2] // 2 + 1, len(self.momenta)
+        G, Gp, S1 = np.zeros(nt), np.zeros((M, nt)), np.zeros(1)
+        n, npc = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.call("sq_phi4_corr_sums", self._h, _dptr(G), _dptr(S1), ctypes.byref(n), _dptr(Gp) if M else None,
+                  ctypes.byref(npc))
+        return {"G": G, "S1": float(S1[0]), "nmeas": n.value, "Gp": Gp, "nmeas_p": npc.value}
+
+    def corr_reset(self):
+        _lib.call("sq_phi4_corr_reset", self._h)
+
+    @staticmethod
+    def measure_shape_info(shape, M=0):
+        """Without a device: {"units_per_plane", "partial_bytes" of the march's [Lz][units][1 + 2 M]
+        doubles, "lds" bytes of the correlator launch (0: slices read from device memory), "nt"} of the
+        in-stream measurements of a lattice of `shape` (sq_phi4_measure_shape_info)."""
+        dims = (ctypes.c_longlong * 3)(*[int(s) for s in shape])
+        out = (ctypes.c_longlong * 4)()
+        _lib.call("sq_phi4_measure_shape_info", dims, int(M), out)
+        return {"units_per_plane": out[0], "partial_bytes": out[1], "lds": out[2], "nt": out[3]}
 
     def hmc_stats(self):
         """[trajectories, accepted, guard trips, leapfrog steps] since creation or hmc_reset()."""
@@ -431,20 +503,31 @@ class Phi4Lattice(_Ctx):
                   labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
         return (bonds, labels) if record else None
 
-    def step_hmc_cluster(self, rounds, ntraj=1, nleap=1, randomize=False, record=False):
+    def step_hmc_cluster(self, rounds, ntraj=1, nleap=1, randomize=False, record=False, every=0, correlate=False,
+                         momenta=False):
         """`rounds` times: `step_hmc(ntraj, nleap, randomize)`, then one `cluster` sweep, all enqueued
         back to back (sq_phi4_step_hmc_cluster): bit for bit the loop of the two calls.  record=True:
         returns (rec_hmc, bonds, labels), the (rounds * ntraj, 4) records of `step_hmc` and the
-        (rounds, sites) records of `cluster`, after one synchronisation; else None without one."""
+        (rounds, sites) records of `cluster`, after one synchronisation; else None without one.
+
+        every >= 1: one in-stream measurement behind the sweep of each every-th round, as in `step_hmc`
+        (sq_phi4_step_hmc_cluster_meas); returns the (rounds // every, 4) series, or (series, rec_hmc,
+        bonds, labels) with record."""
+        every, bits = self._measure_bits(every, correlate, momenta)
         rounds, ntraj = int(rounds), int(ntraj)
         nr, nj = max(rounds, 0), max(ntraj, 0)
         rh = np.zeros((nr * nj, 4), dtype=np.float64) if record else None
         bonds, labels = self._cluster_records(nr, record)
-        _lib.call("sq_phi4_step_hmc_cluster", self._h, rounds, ntraj, int(nleap), 1 if randomize else 0,
-                  _dptr(rh) if record and rh.size else None,
-                  bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
-                  labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
-        return (rh, bonds, labels) if record else None
+        recs = (_dptr(rh) if record and rh.size else None,
+                bonds.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if record and bonds.size else None,
+                labels.ctypes.data_as(ctypes.POINTER(ctypes.c_int)) if record and labels.size else None)
+        if every < 1:
+            _lib.call("sq_phi4_step_hmc_cluster", self._h, rounds, ntraj, int(nleap), 1 if randomize else 0, *recs)
+            return (rh, bonds, labels) if record else None
+        series = np.zeros((nr // every, 4), dtype=np.float64)
+        _lib.call("sq_phi4_step_hmc_cluster_meas", self._h, rounds, ntraj, int(nleap), 1 if randomize else 0, every,
+                  _dptr(series) if series.size else None, bits, *recs)
+        return (series, rh, bonds, labels) if record else series
 
     def cluster_stats(self):
         """[sweeps, clusters, flipped clusters, flipped sites, unconverged sweeps] since creation or
