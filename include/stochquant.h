@@ -975,6 +975,41 @@ int sq_phi4_corr_sums(sq_ctx *ctx, double *G, double *S1, long long *nmeas, doub
 int sq_phi4_corr_reset(sq_ctx *ctx);
 int sq_phi4_measure_shape_info(const long long dims[3], int M, long long out[4]);
 
+/* Heun steps of the single lattice: the second-order Langevin step of the
+ * ensemble (the block above sq_phi4_ens_step_heun is the definition: p =
+ * E_s(phi), e = E_s(p) at the same counter and so with the same normals, phi'
+ * = guard(0.5f (phi + e)), the counter advancing by one), for a PHI4 context
+ * of one periodic slab (comm none), whose field lives in device memory
+ * (DESIGN.md §4.7).  ABI 6: symbols added, none changed.  The context is bit
+ * for bit replica r of an ensemble with the same seed, parameters and counter.
+ *
+ * One Heun step is two launches on the step stream and uses the context's two
+ * field buffers only.  The first is the plain single Euler step of sq_step
+ * from the current buffer F into the idle one P.  The second reads p with its
+ * six neighbours from P and phi at the site itself from F, draws the step's
+ * normals again from the same Philox counter and key, and stores phi' in
+ * place over phi.  In place is safe because F is read only at the site, by
+ * the lane that later stores there, the load ahead of the store in program
+ * order, while every neighbour read goes to P, which that launch does not
+ * write.  The current buffer is the same one before and after a Heun step.
+ * Raw steps keep no guard flag, as sq_step keeps none outside frames; the
+ * clamp acts in all three stages.
+ *
+ * sq_phi4_step_heun: nsteps Heun steps, enqueued without waiting, as sq_step
+ * does.  A model other than PHI4 or a comm other than none: SQ_E_STATE; a null
+ * handle or nsteps < 0: SQ_E_ARG; decided before anything is launched, the
+ * handle left as it was.  nsteps = 0 does nothing.  Calls split in any way
+ * give the same bits; Heun steps, Euler steps, trajectories, sweeps and
+ * measurements alternate freely on one handle.  sq_perf counts one step (and
+ * one site update per site) per Heun step, although each does the work of two.
+ *
+ * sq_phi4_step_heun_meas: the same, with one measurement of the field behind
+ * each every-th Heun step of the call; every, series and measure are those of
+ * sq_phi4_step_hmc_meas, counting Heun steps (series has nsteps / every rows). */
+int sq_phi4_step_heun(sq_ctx *ctx, int nsteps);
+int sq_phi4_step_heun_meas(sq_ctx *ctx, int nsteps, int every, double *series /*[nsteps / every][4], nullable*/,
+                           int measure);
+
 /* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
  * replicas of a ladder swap their fields with a Metropolis test, decided and
  * carried out on the device.  ABI 6: symbols added, none

@@ -414,6 +414,11 @@ int phi4_hmc_reserve(sq_ctx *c, size_t rows);
 int phi4_hmc_enqueue(sq_ctx *c, int ntraj, int nleap, int randomize, size_t row0, bool rec);
 int phi4_hmc_fetch(sq_ctx *c, double *rec, size_t rows);
 
+// sq_phi4_heun.cpp
+// sq_phi4_step_heun in parts: every check; nsteps Heun steps (two launches each) enqueued at the context's counter
+int phi4_heun_check(sq_ctx *c, int nsteps);
+int phi4_heun_enqueue(sq_ctx *c, int nsteps);
+
 // sq_phi4_cluster.cpp
 void release_cluster(sq_ctx *c);
 // sq_phi4_step_hmc_cluster's sweep in parts: every check; the buffers and `rec_sweeps` record rows; one sweep

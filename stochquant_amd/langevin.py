@@ -385,8 +385,28 @@ class Phi4Lattice(_Ctx):
     def local_shape(self):
         return (self.nz_local, self.shape[1], self.shape[0])  # numpy order: z, y, x
 
-    def step(self, n=1):
-        _lib.call("sq_step", self._h, int(n))
+    def step(self, n=1, scheme="euler", every=0, correlate=False, momenta=False):
+        """n Langevin steps, enqueued without waiting for the device.  scheme="euler": sq_step.
+        scheme="heun" (a comm="none" lattice): the ensemble's second-order step, bit for bit, with the
+        field in device memory (sq_phi4_step_heun): two launches per step, the result in place.
+
+        With "heun", every >= 1 puts one in-stream measurement (`measure`) behind each every-th step
+        (sq_phi4_step_heun_meas) and returns the (n // every, 4) series of `sums` rows; correlate /
+        momenta: the measurements also add to the accumulators of `corr_sums()`."""
+        if scheme not in ("euler", "heun"):
+            raise ValueError(f'scheme must be "euler" or "heun", not {scheme!r}')
+        if scheme == "euler":
+            if every or correlate or momenta:
+                raise ValueError('every, correlate and momenta need scheme="heun"')
+            _lib.call("sq_step", self._h, int(n))
+            return None
+        every, bits = self._measure_bits(every, correlate, momenta)
+        if every < 1:
+            _lib.call("sq_phi4_step_heun", self._h, int(n))
+            return None
+        series = np.zeros((max(int(n), 0) // every, 4), dtype=np.float64)
+        _lib.call("sq_phi4_step_heun_meas", self._h, int(n), every, _dptr(series) if series.size else None, bits)
+        return series
 
     @staticmethod
     def _measure_bits(every, correlate, momenta):
