@@ -1010,6 +1010,50 @@ int sq_phi4_step_heun(sq_ctx *ctx, int nsteps);
 int sq_phi4_step_heun_meas(sq_ctx *ctx, int nsteps, int every, double *series /*[nsteps / every][4], nullable*/,
                            int measure);
 
+/* The same Heun step as ONE launch, for rows of 256 S sites.
+ * ABI 6: symbols added, none changed.  Definition: with E_s the Euler step of
+ * sq_step at counter s (the site update and its guard),
+ *     p    = E_s(phi)
+ *     e    = E_s(p)         the same counter, so the same normals
+ *     phi' = guard(0.5f (phi + e))
+ * with one fp32 add and one fp32 multiply per site in the average, and the
+ * counter advancing by one: the bits of sq_phi4_step_heun.
+ *
+ * Order of operations.  A block owns a 256-site x-segment of 8 rows of a
+ * z-chunk and marches the chunk's planes once.  At plane z it loads input
+ * plane z+1, draws the normals of plane z's sites once, forms p on plane z
+ * (on its 8 rows, the two rows beside them and, for rows wider than 256
+ * sites, the sites just outside the segment) and hands it to the neighbouring
+ * rows through LDS; behind one barrier it forms e on plane z-1 from p on
+ * planes z-2, z-1 and z with the normals kept from the iteration before,
+ * averages with phi on plane z-1, which is still in registers, and stores
+ * phi' to plane z-1 of the idle buffer.  The launch reads the current buffer
+ * and writes the other, which becomes the current one: 8 bytes per site
+ * against the 20 of the two launches.  Chunk-edge planes and halo rows of p
+ * are computed by each block that needs them, to the same bits.
+ *
+ * sq_phi4_step_heun_fused: nsteps such steps, enqueued without waiting.
+ * Served: Lx % 256 == 0, Ly % 8 == 0, Lz >= 2, on a PHI4 context of one
+ * periodic slab (comm none) created with the two-step path on (SQ_FUSE2 not
+ * 0); SQ_FUSE2_Z pins the planes per block as it does for sq_step.  Anything
+ * else: SQ_E_STATE naming the cause; a null handle or nsteps < 0: SQ_E_ARG;
+ * decided before anything is launched.  One step is one launch; sq_perf
+ * counts it as sq_phi4_step_heun's.  Fused and two-launch Heun steps, Euler
+ * steps, trajectories, sweeps and measurements alternate freely.
+ *
+ * sq_phi4_step_heun_fused_meas: sq_phi4_step_heun_meas with the fused step
+ * between the measurements; every, series and measure are the same.
+ *
+ * sq_phi4_heun_fused_shape_info (no device, no handle): dims = {Lx, Ly, Lz},
+ * info[0] = 1 when the shape is served, else 0 (info[1], info[2] then 0);
+ * info[1] = 1 for the wide instance (Lx > 256: the x-halo wave), 0 narrow;
+ * info[2] = 1 when a padded field buffer is below 2^31 bytes and the launch
+ * addresses it through one buffer descriptor. */
+int sq_phi4_step_heun_fused(sq_ctx *ctx, int nsteps);
+int sq_phi4_step_heun_fused_meas(sq_ctx *ctx, int nsteps, int every, double *series /*[nsteps / every][4], nullable*/,
+                                 int measure);
+int sq_phi4_heun_fused_shape_info(const int *dims /*[3]*/, int *info /*[3]*/);
+
 /* Replica exchange (parallel tempering) of the phi^4 ensemble: neighbouring
  * replicas of a ladder swap their fields with a Metropolis test, decided and
  * carried out on the device.  ABI 6: symbols added, none

@@ -246,6 +246,9 @@ SIGNATURES = {
     "sq_phi4_step_hmc_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, _D]),
     "sq_phi4_step_heun": (ctypes.c_int, [_P, ctypes.c_int]),
     "sq_phi4_step_heun_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int]),
+    "sq_phi4_step_heun_fused": (ctypes.c_int, [_P, ctypes.c_int]),
+    "sq_phi4_step_heun_fused_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int]),
+    "sq_phi4_heun_fused_shape_info": (ctypes.c_int, [_I, _I]),
     "sq_phi4_step_hmc_cluster_meas": (ctypes.c_int, [_P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                      _D, ctypes.c_int, _D, ctypes.POINTER(ctypes.c_ubyte),
                                                      ctypes.POINTER(ctypes.c_int)]),

@@ -418,6 +418,9 @@ int phi4_hmc_fetch(sq_ctx *c, double *rec, size_t rows);
 // sq_phi4_step_heun in parts: every check; nsteps Heun steps (two launches each) enqueued at the context's counter
 int phi4_heun_check(sq_ctx *c, int nsteps);
 int phi4_heun_enqueue(sq_ctx *c, int nsteps);
+// sq_phi4_step_heun_fused in the same parts (one launch per step; the shape and the two-step path are checked too)
+int phi4_heun_fused_check(sq_ctx *c, int nsteps);
+int phi4_heun_fused_enqueue(sq_ctx *c, int nsteps);
 
 // sq_phi4_cluster.cpp
 void release_cluster(sq_ctx *c);

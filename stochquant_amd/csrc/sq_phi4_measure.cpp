@@ -1,5 +1,5 @@
 // sq_phi4_measure.cpp -- in-stream measurements of the single phi^4 lattice: sq_phi4_set_momenta,
-// sq_phi4_get_momenta, sq_phi4_measure, sq_phi4_step_hmc_meas, sq_phi4_step_heun_meas, sq_phi4_step_hmc_cluster_meas, sq_phi4_corr_sums,
+// sq_phi4_get_momenta, sq_phi4_measure, sq_phi4_step_hmc_meas, sq_phi4_step_heun_meas, sq_phi4_step_heun_fused_meas, sq_phi4_step_hmc_cluster_meas, sq_phi4_corr_sums,
 // sq_phi4_corr_reset, sq_phi4_measure_shape_info (include/stochquant.h; the kernels and the order of every sum
 // are sq_phi4_measure.hip's).  A measurement is three launches on the slab's step stream; the host reads nothing
 // back between them, nor between the trajectories, sweeps and measurements of a call.
@@ -248,8 +248,10 @@ int sq_phi4_step_hmc_meas(sq_ctx *c, int ntraj, int nleap, int randomize, int ev
     return SQ_OK;
 }
 
-int sq_phi4_step_heun_meas(sq_ctx *c, int nsteps, int every, double *series, int measure) {
-    int rc = phi4_heun_check(c, nsteps);
+// The loop of sq_phi4_step_heun_meas and sq_phi4_step_heun_fused_meas: check / enqueue are the step's parts.
+static int heun_meas(sq_ctx *c, int nsteps, int every, double *series, int measure, int (*check)(sq_ctx *, int),
+                     int (*enqueue)(sq_ctx *, int)) {
+    int rc = check(c, nsteps);
     if (!rc) rc = meas_call_check(c, every, measure);
     if (rc || nsteps == 0) return rc;
     DeviceGuard g(c->dev);
@@ -257,13 +259,21 @@ int sq_phi4_step_heun_meas(sq_ctx *c, int nsteps, int every, double *series, int
     const int M = (measure & 2) ? c->mz_M : 0;
     rc = meas_reserve(c, M, rows);
     for (int t = 0; t < nsteps && !rc; ++t) {
-        rc = phi4_heun_enqueue(c, 1);
+        rc = enqueue(c, 1);
         if (!rc && (t + 1) % every == 0) rc = meas_enqueue(c, M, c->mz_series + 4 * (size_t)((t + 1) / every - 1), false, measure);
     }
     if (!rc && series && rows) rc = series_fetch(c, series, rows);
     if (rc) return rc;
     if (series && rows) SQ_HIP(hipStreamSynchronize(c->slabs[0].sA));
     return SQ_OK;
+}
+
+int sq_phi4_step_heun_meas(sq_ctx *c, int nsteps, int every, double *series, int measure) {
+    return heun_meas(c, nsteps, every, series, measure, phi4_heun_check, phi4_heun_enqueue);
+}
+
+int sq_phi4_step_heun_fused_meas(sq_ctx *c, int nsteps, int every, double *series, int measure) {
+    return heun_meas(c, nsteps, every, series, measure, phi4_heun_fused_check, phi4_heun_fused_enqueue);
 }
 
 int sq_phi4_step_hmc_cluster_meas(sq_ctx *c, int nrounds, int ntraj, int nleap, int randomize, int every, double *series,

@@ -385,28 +385,45 @@ class Phi4Lattice(_Ctx):
     def local_shape(self):
         return (self.nz_local, self.shape[1], self.shape[0])  # numpy order: z, y, x
 
-    def step(self, n=1, scheme="euler", every=0, correlate=False, momenta=False):
+    def step(self, n=1, scheme="euler", every=0, correlate=False, momenta=False, fused=False):
         """n Langevin steps, enqueued without waiting for the device.  scheme="euler": sq_step.
         scheme="heun" (a comm="none" lattice): the ensemble's second-order step, bit for bit, with the
         field in device memory (sq_phi4_step_heun): two launches per step, the result in place.
 
         With "heun", every >= 1 puts one in-stream measurement (`measure`) behind each every-th step
         (sq_phi4_step_heun_meas) and returns the (n // every, 4) series of `sums` rows; correlate /
-        momenta: the measurements also add to the accumulators of `corr_sums()`."""
+        momenta: the measurements also add to the accumulators of `corr_sums()`.
+
+        fused=True (with "heun"): the same step, bit for bit, as one launch per step
+        (sq_phi4_step_heun_fused, sq_phi4_step_heun_fused_meas) on the shapes of
+        `heun_fused_shape_info`; any other shape or lattice raises StochQuantError and launches nothing."""
         if scheme not in ("euler", "heun"):
             raise ValueError(f'scheme must be "euler" or "heun", not {scheme!r}')
         if scheme == "euler":
             if every or correlate or momenta:
                 raise ValueError('every, correlate and momenta need scheme="heun"')
+            if fused:
+                raise ValueError('fused needs scheme="heun"')
             _lib.call("sq_step", self._h, int(n))
             return None
         every, bits = self._measure_bits(every, correlate, momenta)
+        fn = "sq_phi4_step_heun_fused" if fused else "sq_phi4_step_heun"
         if every < 1:
-            _lib.call("sq_phi4_step_heun", self._h, int(n))
+            _lib.call(fn, self._h, int(n))
             return None
         series = np.zeros((max(int(n), 0) // every, 4), dtype=np.float64)
-        _lib.call("sq_phi4_step_heun_meas", self._h, int(n), every, _dptr(series) if series.size else None, bits)
+        _lib.call(fn + "_meas", self._h, int(n), every, _dptr(series) if series.size else None, bits)
         return series
+
+    @staticmethod
+    def heun_fused_shape_info(shape):
+        """Whether step(scheme="heun", fused=True) serves a lattice of `shape` and with which kernel instance
+        (sq_phi4_heun_fused_shape_info; no device needed): {"supported", "wide" (rows of more than 256 sites),
+        "one_descriptor" (a padded buffer below 2^31 bytes)}."""
+        dims = (ctypes.c_int * 3)(*(int(s) for s in shape))
+        out = (ctypes.c_int * 3)()
+        _lib.call("sq_phi4_heun_fused_shape_info", dims, out)
+        return {"supported": bool(out[0]), "wide": bool(out[1]), "one_descriptor": bool(out[2])}
 
     @staticmethod
     def _measure_bits(every, correlate, momenta):
